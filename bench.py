@@ -10,11 +10,15 @@ region.
          GPUs (4096 / N scenes per GPU, strong scaling): one process per GPU
          (`--gpus N` spawns them through torch.distributed.run when it is
          not already running under it), scenes sharded, RCCL all-reduce of the
-         G / D gradients once per optimizer step.  The N = 1 line carries the
+         G / D gradients once per optimizer step.  The N = 1 `--full` line has the
          same 4096-scene workload on one GPU as `scaling_reference`, the
          denominator of that strong-scaling curve.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times
+`--steps` iterations and prints the headline fields (metric, value, unit,
+ms_per_step, dtype, config); `--dump-outputs DIR` adds what the last timed
+step computed (its loss values and the G / D parameters it left), one
+float32 `DIR/<name>.npy` per array.  Everything else needs `--full`:
   kernels      every instrumented kernel's device time per iteration
                (HIP events on its launch stream, LaunchTimer in sgan/kernels.py);
   roofline     the dominant one (most device time per iteration) against its
@@ -37,6 +41,7 @@ import argparse
 import glob
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
@@ -86,6 +91,7 @@ LEGS = {
 def build_models(seed, graph="gat"):
     from sgan.models import TrajectoryDiscriminator, TrajectoryGenerator
     torch.manual_seed(seed)
+    random.seed(seed)   # the steps' label smoothing draws (Python's RNG): the same inputs on every run
     g = TrajectoryGenerator(8, 12, embedding_dim=16, encoder_h_dim=32, decoder_h_dim=32, mlp_dim=64, num_layers=1,
                             noise_dim=(8,), noise_type="gaussian", noise_mix_type="global", pooling_type="pool_net",
                             pool_every_timestep=False, dropout=0.0, bottleneck_dim=8, batch_norm=False,
@@ -492,7 +498,8 @@ def spawn(n):
 
 
 def make_step(trainer, batch, sc, batch_g, sc_g, kw, graph, world=1):
-    """-> (run(k): k training iterations, graphed?, the one-iteration
+    """-> (run(k): k training iterations, returning the last one's loss
+    dicts; graphed?; the one-iteration
     GraphedTrainer or None).  Graphed on one rank: a
     HIP graph of GRAPH_ITERS iterations replayed k // GRAPH_ITERS times (the
     per-replay graph launch paid once per GRAPH_ITERS iterations) and a
@@ -532,23 +539,29 @@ def make_step(trainer, batch, sc, batch_g, sc_g, kw, graph, world=1):
                 g1.step()
 
             def run(k):
+                out = None
                 if gk is not None:
                     for _ in range(k // GRAPH_ITERS):
-                        gk.step()
+                        out = gk.step()
                     k %= GRAPH_ITERS
                 for _ in range(k):
-                    g1.step()
+                    out = g1.step()
+                return out
             return run, True, g1
         print("bench: graph capture failed (%s: %s); running eager" % (type(err).__name__, err), file=sys.stderr)
         g1 = gk = None
         torch.cuda.synchronize()
     def eager(k):
+        out = None
         for _ in range(k):
-            trainer.step(batch, sc, batch_g, sc_g, **kw)
+            out = trainer.step(batch, sc, batch_g, sc_g, **kw)
+        return out
     return eager, False, None
 
 
 def timed_run(run, steps, warmup, world, dev, on_start=None):
+    """-> (seconds the `steps` timed iterations took, max over ranks; the last
+    iteration's loss dicts)."""
     run(warmup)
     torch.cuda.synchronize()
     if world > 1:
@@ -557,7 +570,7 @@ def timed_run(run, steps, warmup, world, dev, on_start=None):
     if on_start is not None:
         on_start()
     t0 = time.perf_counter()
-    run(steps)   # exactly `steps` iterations
+    out = run(steps)   # exactly `steps` iterations
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     if world > 1:
@@ -567,7 +580,7 @@ def timed_run(run, steps, warmup, world, dev, on_start=None):
         t = torch.tensor([elapsed])
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    return elapsed
+    return elapsed, out
 
 
 def setup(per_gpu, peds, rank, world, dev, graph_kind):
@@ -587,12 +600,41 @@ def setup(per_gpu, peds, rank, world, dev, graph_kind):
     return trainer, batch, sc, batch_g, sc_g, kw
 
 
-def measure(spec, steps, warmup, rank, world, dev, graph_on, n_it=3):
-    """Time `steps` iterations of one configuration (HIP-graph replays), then
-    every instrumented launch of n_it eager iterations on the same inputs,
-    re-issued back to back between HIP events on its launch stream (graph
-    replays carry no events); rocprofv3's kernel trace of the same command
-    is the cross-check (profiles/)."""
+DUMP_LIMIT = 64 << 20   # bytes --dump-outputs may write in all
+
+
+def step_outputs(losses, trainer):
+    """{name: float32 array} of what one training iteration hands its caller:
+    the D-step's and the G-step's loss values (the dicts step() returns) and
+    the G / D parameters its two Adam updates left."""
+    out = {}
+    for tag, vals in zip(("loss_d", "loss_g"), losses):
+        for k, v in vals.items():
+            out["%s.%s" % (tag, k)] = v
+    for tag, mod in (("G", trainer.G), ("D", trainer.D)):
+        for k, p in mod.named_parameters():
+            out["%s.%s" % (tag, k)] = p
+    torch.cuda.synchronize()
+    return {k: v.detach().to("cpu", torch.float32).numpy().reshape(-1 if v.dim() == 0 else tuple(v.shape))
+            for k, v in out.items()}
+
+
+def dump_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def measure(spec, steps, warmup, rank, world, dev, graph_on, n_it=3, full=True, keep_outputs=False):
+    """Time `steps` iterations of one configuration (HIP-graph replays); with
+    keep_outputs, copy out what the last of them computed (step_outputs).
+    full: then every instrumented launch of n_it eager iterations on the same
+    inputs, re-issued back to back between HIP events on its launch stream
+    (graph replays carry no events); rocprofv3's kernel trace of the same
+    command is the cross-check (profiles/)."""
     from sgan import kernels as K
     K.set_precision(spec["prec"])
     try:
@@ -602,8 +644,13 @@ def measure(spec, steps, warmup, rank, world, dev, graph_on, n_it=3):
         # all-reduce between the graph segments; captured collectives (RCCL,
         # inside the graph): the same two flat buckets all-reduced eagerly
         # after the timed run -- on this rank, max over ranks
-        comm = gt is not None and world > 1 and trainer.dp.segmented
-        elapsed = timed_run(step, steps, warmup, world, dev, on_start=gt.time_allreduce if comm else None)
+        comm = full and gt is not None and world > 1 and trainer.dp.segmented
+        elapsed, losses = timed_run(step, steps, warmup, world, dev, on_start=gt.time_allreduce if comm else None)
+        outputs = step_outputs(losses, trainer) if keep_outputs and losses is not None else None
+        res = dict(elapsed=elapsed, graphed=graphed, outputs=outputs,
+                   captured=bool(graphed and world > 1 and not trainer.dp.segmented), transport=trainer.dp.transport)
+        if not full:
+            return res
         ar_us = gt.allreduce_ms() * 1e3 / steps if comm else None
         if comm:
             gt.time_allreduce(False)
@@ -621,9 +668,7 @@ def measure(spec, steps, warmup, rank, world, dev, graph_on, n_it=3):
         timed = K.timer.replay(recs)
     finally:
         K.set_precision("fp32")
-    return dict(elapsed=elapsed, graphed=graphed, agg=kernel_table(timed, n_it), recs=recs, n_it=n_it,
-                allreduce_us=ar_us, captured=bool(graphed and world > 1 and not trainer.dp.segmented),
-                transport=trainer.dp.transport)
+    return dict(res, agg=kernel_table(timed, n_it), recs=recs, n_it=n_it, allreduce_us=ar_us)
 
 
 def bucket_allreduce_us(trainer, dev, reps=20):
@@ -684,6 +729,13 @@ def main():
     ap.add_argument("--peds", type=int, default=20)
     ap.add_argument("--graph-kind", dest="graph_kind", default="gat", choices=["gat", "gcn", "sgangat"])
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel device times and rooflines, the CPU baseline, the other "
+                         "BASELINE configurations, the scaling reference, the real-data leg, the all-reduce "
+                         "times (N > 1) and the detail file (each can be switched off with its --no-... option)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss values, G / D parameters) "
+                         "as DIR/<name>.npy (float32)")
     ap.add_argument("--leg", default="", choices=[""] + list(LEGS),
                     help="measure this BASELINE configuration as the headline (e.g. for its PMC passes)")
     ap.add_argument("--no-legs", action="store_true", help="skip the other configurations (N = 1)")
@@ -698,6 +750,8 @@ def main():
     ap.add_argument("--pmc-kernel", default="",
                     help="with --pmc-target: re-issue this kernel's main launch (default: the dominant one here)")
     args = ap.parse_args()
+    if args.pmc_target > 0 and not args.full:
+        ap.error("--pmc-target re-issues a kernel of the per-kernel table: it needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn(args.gpus))
@@ -731,8 +785,56 @@ def main():
     else:
         per_gpu = args.batch or (64 if world == 1 else CONFIG4_GLOBAL // world)
         head = dict(per_gpu=per_gpu, peds=args.peds, graph=args.graph_kind, prec=args.precision)
+    res = measure(head, args.steps, args.warmup, rank, world, dev, args.graph, full=args.full,
+                  keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if res["outputs"] is not None:
+        dump_outputs(args.dump_outputs, res.pop("outputs"))
+    if args.full:
+        full_report(args, head, res, rank, world, dev)
+    elif rank == 0:
+        print(json.dumps(headline(args, head, res, world)), flush=True)
+    if world > 1:
+        import gc
+        from sgan import rccl
+        del res
+        gc.collect()   # the captured graphs are gone before their communicator
+        torch.cuda.synchronize()
+        dist.barrier()
+        rccl.release()
+        dist.destroy_process_group()
+
+
+def headline(args, head, res, world):
+    """The result line of a plain run: the timed steps' rate and what was timed."""
     per_gpu = head["per_gpu"]
-    res = measure(head, args.steps, args.warmup, rank, world, dev, args.graph)
+    ms_step = res["elapsed"] / args.steps * 1e3
+    value = world * per_gpu / (res["elapsed"] / args.steps)
+    is_c1 = world == 1 and (per_gpu, head["peds"], head["graph"], head["prec"]) == (64, 20, "gat", "fp32")
+    return {
+        "metric": METRIC, "value": round(value, 2), "unit": "scenes/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
+        "scaling": "weak" if world == 1 else "strong",
+        "vs_baseline": round(value / REFERENCE_CPU_SCENES_S, 1) if is_c1 else None,
+        "vs_baseline_basis": "value / 13.9 scenes/s, the reference's CPU path on this workload in the survey "
+                             "container (BASELINE.md 2); no published throughput" if is_c1 else None,
+        "dtype": head["prec"],
+        "data": "synthetic (random-init weights, SURVEY.md 8d recipe)",
+        "config": {"workload": "train iteration = D-step + G-step (best_k=20, Adam), %s generator%s" % (
+                                   head["graph"].upper(),
+                                   "; BASELINE configs[1] shape (batch 64)" if is_c1 else
+                                   "; BASELINE configs[3] (4096-scene global batch)"
+                                   if world * per_gpu == CONFIG4_GLOBAL else
+                                   "; %s" % head.get("what", "")),
+                   "scenes_per_gpu": per_gpu, "global_batch": per_gpu * world, "peds_per_scene": head["peds"],
+                   "obs_len": 8, "pred_len": 12, "generator": head["graph"], "hip_graph": res["graphed"],
+                   "parallelism": "dp%d" % world},
+    }
+
+
+def full_report(args, head, res, rank, world, dev):
+    """--full: everything measured beside the headline, the detail file and the
+    result line with their summaries."""
+    per_gpu = head["per_gpu"]
     elapsed, agg, recs = res["elapsed"], res["agg"], res["recs"]
     pmc_target = None
     if args.pmc_target > 0 and rank == 0:
@@ -774,7 +876,7 @@ def main():
         tr4, b4, sc4, bg4, scg4, kw4 = setup(CONFIG4_GLOBAL, args.peds, 0, 1, dev, "gat")
         st4, gr4, _ = make_step(tr4, b4, sc4, bg4, scg4, kw4, args.graph)
         k4 = max(3, args.steps // 4)
-        e4 = timed_run(st4, k4, 2, 1, dev)
+        e4, _ = timed_run(st4, k4, 2, 1, dev)
         scaling_ref = {"global_batch": CONFIG4_GLOBAL, "n_gpus": 1, "steps": k4, "ms_per_step": round(e4 / k4 * 1e3, 3),
                        "value": round(CONFIG4_GLOBAL / (e4 / k4), 2), "unit": "scenes/s", "hip_graph": gr4,
                        "note": "BASELINE configs[3] workload on one GPU: strong-scaling efficiency at N GPUs = "
@@ -809,38 +911,20 @@ def main():
                     f.write("%-50s %-36s %5.2f %8.2f %8.1f %12.4g %12.4g %8.3f\n" % (
                         n[:50], str(list(k[1:]))[:36], r["launches"] / n_it, r["ms"] * 1e3, us, r["flop"],
                         r["bytes"], rl))
-        ms_step = elapsed / args.steps * 1e3
-        value = world * per_gpu / (elapsed / args.steps)
         cpu = None
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(per_gpu, head["peds"], iters=args.cpu_iters)
-        is_c1 = world == 1 and (per_gpu, head["peds"], head["graph"], head["prec"]) == (64, 20, "gat", "fp32")
-        # everything beyond the driver's fields goes to a side file named in
+        # everything beyond the headline's fields goes to a side file named in
         # the line: the stdout line stays a few KB
         detail_path = os.environ.get("SGG_BENCH_DETAIL") or os.path.join(
-            ROOT, "gpurun_out", "bench_detail_n%d_%d.json" % (world, os.getpid()))
+            ROOT, "bench_out", "bench_detail_n%d_%d.json" % (world, os.getpid()))
         detail = {"roofline": roofline, "iteration_roofline": it_roof, "kernels": top_kernels(agg, 24),
                   "launch_table": launch_table, "cpu_baseline": cpu, "legs": legs, "scaling_reference": scaling_ref,
                   "real_data": real, "pmc_target": pmc_target}
-        line = {
-            "metric": METRIC, "value": round(value, 2), "unit": "scenes/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
-            "scaling": "weak" if world == 1 else "strong",
-            "vs_baseline": round(value / REFERENCE_CPU_SCENES_S, 1) if is_c1 else None,
-            "vs_baseline_basis": "value / 13.9 scenes/s, the reference's CPU path on this workload in the survey "
-                                 "container (BASELINE.md 2); no published throughput" if is_c1 else None,
+        line = headline(args, head, res, world)
+        ms_step, value = elapsed / args.steps * 1e3, line["value"]
+        line |= {
             "vs_cpu_same_box": round(value / cpu["value"], 1) if cpu else None,
-            "dtype": head["prec"],
-            "data": "synthetic (random-init weights, SURVEY.md 8d recipe)",
-            "config": {"workload": "train iteration = D-step + G-step (best_k=20, Adam), %s generator%s" % (
-                                       head["graph"].upper(),
-                                       "; BASELINE configs[1] shape (batch 64)" if is_c1 else
-                                       "; BASELINE configs[3] (4096-scene global batch)"
-                                       if world * per_gpu == CONFIG4_GLOBAL else
-                                       "; %s" % head.get("what", "")),
-                       "scenes_per_gpu": per_gpu, "global_batch": per_gpu * world, "peds_per_scene": head["peds"],
-                       "obs_len": 8, "pred_len": 12, "generator": head["graph"], "hip_graph": res["graphed"],
-                       "parallelism": "dp%d" % world},
             "roofline": {k: roofline[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel",
                                                   "launch", "avg_launch_us", "flop_per_launch",
                                                   "algorithmic_bytes_per_launch", "traffic_over_algorithmic")},
@@ -889,14 +973,6 @@ def main():
         except OSError as e:
             line["detail"] = "unwritten (%s)" % e
         print(json.dumps(line), flush=True)
-    if world > 1:
-        import gc
-        from sgan import rccl
-        gc.collect()   # the captured graphs are gone before their communicator
-        torch.cuda.synchronize()
-        dist.barrier()
-        rccl.release()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -93,7 +93,8 @@ def test_bench_gpus2_spawns_two_ranks():
     env = dict(os.environ, SGG_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "16", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, env=env)
+                        "--batch", "16", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240,
+                       env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines[-1]) <= 6144, "the bench line must stay parseable: %d bytes" % len(lines[-1])

@@ -8,8 +8,8 @@ shift 2
 mkdir -p $O
 cd $R
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --no-legs --no-cpu-baseline --no-scaling-reference --steps 200 --warmup 20 "$@" > $O/base_$i.json 2> $O/base_$i.err || { echo BENCH_FAIL; tail -20 $O/base_$i.err; exit 1; }
-  env $VAR timeout -k 10 300 python bench.py --no-legs --no-cpu-baseline --no-scaling-reference --steps 200 --warmup 20 "$@" > $O/var_$i.json 2> $O/var_$i.err || { echo BENCH_FAIL; tail -20 $O/var_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-legs --no-cpu-baseline --no-scaling-reference --steps 200 --warmup 20 "$@" > $O/base_$i.json 2> $O/base_$i.err || { echo BENCH_FAIL; tail -20 $O/base_$i.err; exit 1; }
+  env $VAR timeout -k 10 300 python bench.py --full --no-legs --no-cpu-baseline --no-scaling-reference --steps 200 --warmup 20 "$@" > $O/var_$i.json 2> $O/var_$i.err || { echo BENCH_FAIL; tail -20 $O/var_$i.err; exit 1; }
 done
 python - "$O" <<'PY'
 import json, sys, glob, os

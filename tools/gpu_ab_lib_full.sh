@@ -2,11 +2,12 @@
 # line (headline, legs, real data; no CPU baseline / scaling reference)
 # usage: bash tools/gpu_ab_lib_full.sh [kernel filter]
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # where the results go (relative to the repository root)
+mkdir -p $OUT
 filt=${1:-pool_bwd}
 for v in a b; do
-  SGG_LIB=$PWD/tools/ab/libsgg_$v.so timeout -k 10 400 python bench.py --steps 60 --no-cpu-baseline --no-scaling-reference > gpurun_out/abf_$v.json 2> gpurun_out/abf_$v.err || { echo BENCH_FAIL; tail -5 gpurun_out/abf_$v.err; exit 1; }
-  python - gpurun_out/abf_$v.json "$v" "$filt" <<'PY'
+  SGG_LIB=$PWD/tools/ab/libsgg_$v.so timeout -k 10 400 python bench.py --full --steps 60 --no-cpu-baseline --no-scaling-reference > $OUT/abf_$v.json 2> $OUT/abf_$v.err || { echo BENCH_FAIL; tail -5 $OUT/abf_$v.err; exit 1; }
+  python - $OUT/abf_$v.json "$v" "$filt" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], "headline %.1f ms %.4f" % (d["value"], d["ms_per_step"]), [(r["kernel"][5:45], r["shape"][1], round(r["avg_us"], 2)) for r in d["launch_table"] if sys.argv[3] in r["kernel"]])

@@ -2,7 +2,7 @@
 
 usage: python tools/pmc_traffic.py FETCH_DIR WRITE_DIR BENCH_JSON OUT_JSON
 
-Both passes run `bench.py ... --pmc-target R`: after its timing, bench
+Both passes run `bench.py --full ... --pmc-target R`: after its timing, bench
 re-issues the dominant kernel's main launch R times, so the LAST R
 dispatches of that kernel name in each counter CSV are exactly that launch
 shape; their mean FETCH_SIZE / WRITE_SIZE is its HBM traffic per launch.
@@ -42,7 +42,7 @@ def main():
     tgt = line["pmc_target"]
     name, reps = tgt["kernel"], tgt["reps"]
     res = json.load(open(out)) if os.path.exists(out) else {}
-    res["source"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate runs) of `bench.py --pmc-target R`; "
+    res["source"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate runs) of `bench.py --full --pmc-target R`; "
                      "the last R dispatches of the target kernel; FETCH_SIZE x2 (gfx950)")
     base = name.split("+")[0]
     match = (lambda k: k == base) if "<" in base else (lambda k: k.split("<")[0] == base)
