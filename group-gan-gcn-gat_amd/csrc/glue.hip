@@ -17,6 +17,7 @@
 //                     scene's peds / sum(loss_mask) (train.py:459-464)
 // All sums run in a fixed order (deterministic).
 #include "sgg_common.h"
+#include "l2_body.h"
 
 namespace sgg {
 
@@ -72,87 +73,18 @@ __global__ void __launch_bounds__(256) decoder_init_kernel(const float* __restri
   }
 }
 
-// Both L2 kernels walk a scene's (step, ped) elements PED-FASTEST, so the gt
-// and pred reads of a wave are contiguous runs (gt / pred are step-major:
-// [T][B][2]); the scene's loss-mask block (ped-major, [B][ldm]) is first
-// staged in LDS with coalesced reads and then read at (ped, step).
-constexpr int kL2MaxElems = SGG_POOL_MAX_PEDS * 32;   // n * T staged per scene (larger: read in place)
+// (stage_mask, l2_scene and the bodies of l2_select_kernel and
+// l2_loss_bwd_scenes_kernel live in l2_body.h: the four-wave LSTM forward
+// launch runs them too, as glue workgroups -- sgg_lstm_fwd_seg_glue)
 
-// the scene's mask block -> msk[i * T + t] (coalesced: t fastest)
-__device__ __forceinline__ void stage_mask(float* msk, const float* __restrict__ mask, int ldm, int o, int n, int T,
-                                           int t0, int nt) {
-  for (int e = t0; e < n * T; e += nt) {
-    const int i = e / T, t = e - i * T;
-    msk[e] = mask[(size_t)(o + i) * ldm + t];
-  }
-}
-
-// one workgroup (8 waves) per scene: wave w takes samples w, w + 8, ...
-// (their loads together); lane = element, the scene sum by a wave shuffle;
-// argmin over the k samples (first minimum, as torch.argmin)
+// one workgroup (8 waves) per scene
 __global__ void __launch_bounds__(512) l2_select_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                         const float* __restrict__ mask, int ldm,
                                                         const int32_t* __restrict__ scene_off, int T, int B, int k,
                                                         int64_t* __restrict__ best) {
-  __shared__ float part[256];   // k <= 256
+  __shared__ float part[kL2MaxK];   // k <= 256
   __shared__ float msk[kL2MaxElems];
-  const int s = blockIdx.x;
-  const int o = scene_off[s], n = scene_off[s + 1] - o;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float2* g2 = reinterpret_cast<const float2*>(gt);
-  const float2* p2 = reinterpret_cast<const float2*>(pred);
-  const int tot = n * T;
-  const bool staged = tot <= kL2MaxElems;   // uniform
-  if (staged) stage_mask(msk, mask, ldm, o, n, T, threadIdx.x, blockDim.x);
-  __syncthreads();
-  constexpr int kRS = 4;
-  for (int r0 = wave; r0 < k; r0 += 8 * kRS) {
-    float acc[kRS];
-#pragma unroll
-    for (int j = 0; j < kRS; ++j) acc[j] = 0.f;
-    // four elements per lane in flight (a 20-ped scene's 240 in one round trip);
-    // the sum runs over e = lane, lane + 64, ... in order, as with any unroll
-    for (int e0 = lane; e0 < tot; e0 += 256) {
-      float mk[4];
-      float2 g[4], q[kRS][4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = min(e0 + 64 * u, tot - 1);
-        const int t = e / n, i = e - t * n, p = o + i;
-        mk[u] = staged ? msk[i * T + t] : mask[(size_t)p * ldm + t];
-        g[u] = g2[(size_t)t * B + p];
-#pragma unroll
-        for (int j = 0; j < kRS; ++j) {
-          const int r = min(r0 + 8 * j, k - 1);
-          q[j][u] = p2[((size_t)t * k + r) * B + p];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kRS; ++j)
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (e0 + 64 * u < tot) {
-            const float dx = g[u].x - q[j][u].x, dy = g[u].y - q[j][u].y;
-            acc[j] = fmaf(mk[u], fmaf(dx, dx, dy * dy), acc[j]);
-          }
-    }
-#pragma unroll
-    for (int j = 0; j < kRS; ++j) {
-      const float a = wave_sum(acc[j]);
-      if (lane == 0 && r0 + 8 * j < k) part[r0 + 8 * j] = a;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int bi = 0;
-    float bv = part[0];
-    for (int r = 1; r < k; ++r)
-      if (part[r] < bv) {
-        bv = part[r];
-        bi = r;
-      }
-    best[s] = bi;
-  }
+  l2_select_body<8>(pred, gt, mask, ldm, scene_off, T, B, k, best, blockIdx.x, part, msk);
 }
 
 // loss = sum_s w * (sum_{i in s, t} m (gt - pred)^2) / (sum_{i in s, t} m)
@@ -161,45 +93,6 @@ __global__ void __launch_bounds__(512) l2_select_kernel(const float* __restrict_
 // terms in scene order (lane-strided partials, a fixed shuffle tree).  A
 // scene without a masked step (only the padding scenes of a fixed-capacity
 // batch, PaddedScenes: real scenes always have one) adds 0 instead of 0 / 0.
-// one wave: the (masked squared error, mask) sums of scene [o, o + n); msk is
-// the wave's own LDS staging buffer (kL2MaxElems)
-__device__ __forceinline__ void l2_scene(const float* __restrict__ pred, int ldp, const float2* __restrict__ g2,
-                                         const float* __restrict__ mask, int ldm, int o, int n, int T, int B,
-                                         float* msk, int lane, float& acc_out, float& ms_out) {
-  const int tot = n * T;
-  const bool staged = tot <= kL2MaxElems;   // uniform
-  if (staged) stage_mask(msk, mask, ldm, o, n, T, lane, 64);
-  // lanes read entries other lanes wrote: a wavefront-scope release / acquire
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  float acc = 0.f, ms = 0.f;
-  for (int e0 = lane; e0 < tot; e0 += 256) {
-    float mk[4];
-    float2 g[4], q[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = min(e0 + 64 * u, tot - 1);
-      const int t = e / n, i = e - t * n, p = o + i;
-      mk[u] = staged ? msk[i * T + t] : mask[(size_t)p * ldm + t];
-      g[u] = g2[(size_t)t * B + p];
-      q[u] = *reinterpret_cast<const float2*>(pred + (size_t)t * ldp + 2 * p);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (e0 + 64 * u < tot) {
-        const float dx = g[u].x - q[u].x, dy = g[u].y - q[u].y;
-        acc = fmaf(mk[u], fmaf(dx, dx, dy * dy), acc);
-        ms += mk[u];
-      }
-  }
-  acc_out = wave_sum(acc);
-  ms_out = wave_sum(ms);
-  // the staging buffer is rewritten by the wave's next scene: every lane's
-  // reads of it are done (wave_sum consumed them) before the next stores
-  __builtin_amdgcn_wave_barrier();
-}
-
 __global__ void __launch_bounds__(64) l2_terms_kernel(const float* __restrict__ pred, int ldp,
                                                       const float* __restrict__ gt, const float* __restrict__ mask,
                                                       int ldm, const int32_t* __restrict__ scene_off, int T, int B,
@@ -254,21 +147,8 @@ __global__ void __launch_bounds__(64) l2_loss_bwd_scenes_kernel(const float* __r
                                                                 float* __restrict__ dpred, int ldd,
                                                                 float* __restrict__ term) {
   __shared__ float msk[kL2MaxElems];
-  const int lane = threadIdx.x, s = blockIdx.x;
-  const int o = scene_off[s], n = scene_off[s + 1] - o;
-  float acc, ms;
-  l2_scene(pred, ldp, reinterpret_cast<const float2*>(gt), mask, ldm, o, n, T, B, msk, lane, acc, ms);
-  if (term && lane == 0) term[s] = ms > 0.f ? (w * acc) / ms : 0.f;   // (l2_terms_kernel's value)
-  const float g = *gout * w * -2.f;
-  const float2* g2 = reinterpret_cast<const float2*>(gt);
-  for (int e = lane; e < n * T; e += 64) {
-    const int t = e / n, p = o + (e - t * n);
-    const float m = mask[(size_t)p * ldm + t];
-    const float2 gv = g2[(size_t)t * B + p];
-    const float2 q = *reinterpret_cast<const float2*>(pred + (size_t)t * ldp + 2 * p);
-    const float c = ms > 0.f ? g * m / ms : 0.f;
-    *reinterpret_cast<float2*>(dpred + (size_t)t * ldd + 2 * p) = make_float2(c * (gv.x - q.x), c * (gv.y - q.y));
-  }
+  l2_bwd_scene_body(pred, ldp, gt, mask, ldm, scene_off, T, B, w, gout, dpred, ldd, term, blockIdx.x, threadIdx.x,
+                    msk);
 }
 
 int grid_for(long long n, int per) {

@@ -350,6 +350,51 @@ extern "C" int sgg_lstm_fwd_seg(const SggLstmSeg* seg, int H, void* stream) {
   return lstm_mw_fwd_seg(to_mw(*seg), H, (hipStream_t)stream);
 }
 
+static int device_cus() {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int d = 0, v = 0;
+    const bool ok = hipGetDevice(&d) == hipSuccess &&
+                    hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess;
+    ncu = ok && v > 0 ? v : 256;
+  }
+  return ncu;
+}
+
+extern "C" int sgg_lstm_fwd_seg_glue(const SggLstmSeg* seg, int H, const SggGlueSeg* glue, void* stream) {
+  SGG_CHECK_ARG(seg && glue, "sgg_lstm_fwd_seg_glue: null segment");
+  SGG_CHECK_ARG(lstm_mw_ok(H, seg->B), "sgg_lstm_fwd_seg_glue: no four-wave kernel for H=%d", H);
+  const SggGlueSeg& g = *glue;
+  SGG_CHECK_ARG(g.kind == SGG_GLUE_NONE || g.kind == SGG_GLUE_SELECT || g.kind == SGG_GLUE_L2BWD,
+                "sgg_lstm_fwd_seg_glue: glue kind %d", g.kind);
+  if (g.kind == SGG_GLUE_SELECT) {   // sgg_l2_select's rules
+    SGG_CHECK_ARG(g.pred && g.gt && g.mask && g.scene_off && g.best, "sgg_lstm_fwd_seg_glue (select): null pointer");
+    SGG_CHECK_ARG(g.S >= 0 && g.T >= 1 && g.B >= 0 && g.k >= 1 && g.k <= 256 && g.ldm >= g.T,
+                  "sgg_lstm_fwd_seg_glue (select): bad sizes");
+  } else if (g.kind == SGG_GLUE_L2BWD) {   // sgg_l2_loss_bwd_scenes' rules
+    SGG_CHECK_ARG(g.pred && g.gt && g.mask && g.scene_off && g.gout && g.dpred,
+                  "sgg_lstm_fwd_seg_glue (l2 backward): null pointer");
+    SGG_CHECK_ARG(g.S >= 0 && g.T >= 1 && g.B >= 0 && g.ldm >= g.T && g.ldp >= 2 * g.B && g.ldd >= 2 * g.B,
+                  "sgg_lstm_fwd_seg_glue (l2 backward): bad sizes");
+  }
+  // The glue workgroups ride where the segment's last round of workgroups leaves them CUs (the H = 48 kernels hold
+  // one workgroup per CU).  Behind a grid that fills the device they would only lengthen its tail, two short
+  // workgroups per CU one after the other, slower than their own launch (512 scenes, [12, 20480]: +8 us per
+  // iteration): the glue body then goes first, in its stand-alone launch -- the same results either way.
+  if (g.kind != SGG_GLUE_NONE && g.S > 0) {
+    const int cus = device_cus(), nblk = (seg->B + 15) / 16, last = nblk % cus;
+    if ((nblk >= cus && last == 0) || last + g.S > cus) {
+      const int rc = g.kind == SGG_GLUE_SELECT
+                         ? sgg_l2_select(g.pred, g.gt, g.mask, g.ldm, g.scene_off, g.S, g.T, g.B, g.k, g.best, stream)
+                         : sgg_l2_loss_bwd_scenes(g.pred, g.ldp, g.gt, g.mask, g.ldm, g.scene_off, g.S, g.T, g.B, g.w,
+                                                  g.gout, g.dpred, g.ldd, g.term, stream);
+      if (rc) return rc;
+      return lstm_mw_fwd_seg(to_mw(*seg), H, (hipStream_t)stream);
+    }
+  }
+  return lstm_mw_fwd_seg(to_mw(*seg), H, (hipStream_t)stream, glue);
+}
+
 extern "C" int sgg_lstm_fwd_seg2(const SggLstmSeg* a, int Ha, const SggLstmSeg* b, int Hb, void* stream) {
   SGG_CHECK_ARG(a && b, "sgg_lstm_fwd_seg2: null segment");
   SGG_CHECK_ARG(lstm_mw_ok(Ha, a->B) && lstm_mw_ok(Hb, b->B), "sgg_lstm_fwd_seg2: no four-wave kernel (Ha=%d Hb=%d)",

@@ -60,6 +60,7 @@
 #include <type_traits>
 
 #include "sgg_common.h"
+#include "l2_body.h"
 
 namespace sgg {
 
@@ -188,8 +189,14 @@ namespace {
 // branches.  A padded lane (ped >= B, last block) runs on the clamped ped's
 // inputs, so it computes bit-identical values and its stores to that ped's
 // rows (h_all, rel_out) are benign duplicates: no store needs a guard.
+//
+// glue != NULL (encoder kernels only, a compile-time constant at every call
+// site): the workgroup is a GLUE workgroup of the launch (sgg.h SggGlueSeg) --
+// it runs scene `blk` of the L2 glue body on this kernel's LDS (the mask stage
+// in relseq, the samples' sums in hx: the static LDS does not grow) and no
+// LSTM work.
 template <int H, bool DEC, bool SAVE>
-__device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk) {
+__device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk, const SggGlueSeg* glue = nullptr) {
   constexpr int MU = MwCfg<H>::MU, KS = MwCfg<H>::KS;
   constexpr bool decoder = DEC, save = SAVE;
   const float* __restrict__ rel = sg.rel;
@@ -231,6 +238,22 @@ __device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk) {
   __shared__ float hst[X3 && SAVE ? 2 : 1][kMwPeds][X3 && SAVE ? kHsP : 1];
   __shared__ float2 rpart[2][4][kMwPeds];
   __shared__ float relseq[kMwMaxT][kMwPeds][2];
+  if constexpr (!DEC) {
+    if (glue) {
+      static_assert(sizeof(relseq) >= kL2MaxElems * sizeof(float) && sizeof(hx) >= kL2MaxK * sizeof(float),
+                    "the glue bodies' LDS is lent by relseq / hx");
+      float* msk = &relseq[0][0][0];
+      if (glue->kind == SGG_GLUE_SELECT) {
+        l2_select_body<kMwThreads / 64>(glue->pred, glue->gt, glue->mask, glue->ldm, glue->scene_off, glue->T,
+                                        glue->B, glue->k, glue->best, blk, reinterpret_cast<float*>(&hx[0][0][0][0]),
+                                        msk);
+      } else if (threadIdx.x < 64) {   // one wave per scene, as the stand-alone kernel; the others are done
+        l2_bwd_scene_body(glue->pred, glue->ldp, glue->gt, glue->mask, glue->ldm, glue->scene_off, glue->T, glue->B,
+                          glue->w, glue->gout, glue->dpred, glue->ldd, glue->term, blk, threadIdx.x, msk);
+      }
+      return;
+    }
+  }
   const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4, c16 = lane & 15;
@@ -719,8 +742,18 @@ __device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk) {
   LMARK(63);
 }
 
+// workgroups [0, nblk) run the segment; an encoder launch may carry gl.S glue
+// workgroups after them (sgg_lstm_fwd_seg_glue: LAST in the grid, so the long
+// LSTM workgroups are dispatched first; the branch is workgroup-uniform and
+// the two bodies share no barrier).  Without glue nblk is the grid.
 template <int H, bool DEC, bool SAVE>
-__global__ void __launch_bounds__(kMwThreads) lstm_mw_fwd_kernel(MwSeg sg) {
+__global__ void __launch_bounds__(kMwThreads) lstm_mw_fwd_kernel(MwSeg sg, SggGlueSeg gl, int nblk) {
+  if constexpr (!DEC) {
+    if ((int)blockIdx.x >= nblk) {
+      mw_fwd_body<H, DEC, SAVE>(sg, blockIdx.x - nblk, &gl);
+      return;
+    }
+  }
   mw_fwd_body<H, DEC, SAVE>(sg, blockIdx.x);
 }
 
@@ -1340,21 +1373,25 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
   LMARK(62);
 }
 
+// glue (encoder segments only): gl->S glue workgroups after the segment's
 template <int H>
-int launch_seg(const MwSeg& sg, bool decoder, hipStream_t st) {
-  const int grid = (sg.B + kMwPeds - 1) / kMwPeds;
+int launch_seg(const MwSeg& sg, bool decoder, hipStream_t st, const SggGlueSeg* glue = nullptr) {
+  const int nblk = (sg.B + kMwPeds - 1) / kMwPeds;
   auto k = decoder ? (sg.act_tile ? lstm_mw_fwd_kernel<H, true, true> : lstm_mw_fwd_kernel<H, true, false>)
                    : (sg.act_tile ? lstm_mw_fwd_kernel<H, false, true> : lstm_mw_fwd_kernel<H, false, false>);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kMwThreads), 0, st, sg);
+  const bool ride = glue && !decoder && glue->kind != SGG_GLUE_NONE && glue->S > 0;
+  SggGlueSeg gl{};
+  if (ride) gl = *glue;
+  hipLaunchKernelGGL(k, dim3(nblk + (ride ? gl.S : 0)), dim3(kMwThreads), 0, st, sg, gl, nblk);
   SGG_RETURN_LAUNCH("sgg_lstm_fwd");
 }
 
-int launch_seg_h(const MwSeg& sg, int H, bool decoder, hipStream_t st) {
+int launch_seg_h(const MwSeg& sg, int H, bool decoder, hipStream_t st, const SggGlueSeg* glue = nullptr) {
   switch (H) {
-    case 16: return launch_seg<16>(sg, decoder, st);
-    case 32: return launch_seg<32>(sg, decoder, st);
-    case 48: return launch_seg<48>(sg, decoder, st);
-    default: return launch_seg<64>(sg, decoder, st);
+    case 16: return launch_seg<16>(sg, decoder, st, glue);
+    case 32: return launch_seg<32>(sg, decoder, st, glue);
+    case 48: return launch_seg<48>(sg, decoder, st, glue);
+    default: return launch_seg<64>(sg, decoder, st, glue);
   }
 }
 
@@ -1430,9 +1467,9 @@ static int seg_check(const MwSeg& s, int H, const char* fn) {
   return 0;
 }
 
-int lstm_mw_fwd_seg(const MwSeg& s, int H, hipStream_t st) {
-  if (int rc = seg_check(s, H, "sgg_lstm_fwd_seg")) return rc;
-  return launch_seg_h(s, H, false, st);
+int lstm_mw_fwd_seg(const MwSeg& s, int H, hipStream_t st, const SggGlueSeg* glue) {
+  if (int rc = seg_check(s, H, glue ? "sgg_lstm_fwd_seg_glue" : "sgg_lstm_fwd_seg")) return rc;
+  return launch_seg_h(s, H, false, st, glue);
 }
 
 int lstm_mw_fwd_seg2(const MwSeg& a, int Ha, const MwSeg& b, int Hb, hipStream_t st) {

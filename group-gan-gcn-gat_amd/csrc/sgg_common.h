@@ -134,7 +134,9 @@ __device__ __forceinline__ float dec_h0(const SggDecInit& d, int p, int u) {
 __device__ __forceinline__ float dec_rel0(const SggDecInit& d, int p, int k) {
   return d.last_rel[(size_t)(p % d.Bper) * 2 + k];
 }
-__attribute__((visibility("hidden"))) int lstm_mw_fwd_seg(const MwSeg& s, int H, hipStream_t st);
+// glue (sgg.h SggGlueSeg, checked by the caller): its S workgroups ride last in the grid
+__attribute__((visibility("hidden"))) int lstm_mw_fwd_seg(const MwSeg& s, int H, hipStream_t st,
+                                                          const SggGlueSeg* glue = nullptr);
 __attribute__((visibility("hidden"))) int lstm_mw_fwd_seg2(const MwSeg& a, int Ha, const MwSeg& b, int Hb,
                                                            hipStream_t st);
 __attribute__((visibility("hidden"))) int lstm_mw_fwd_dec_seg(const float* A, const float* Whh, const float* bias,

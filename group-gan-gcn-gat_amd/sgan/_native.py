@@ -64,6 +64,16 @@ class LstmSeg(ctypes.Structure):
 
 _sargs = ctypes.POINTER(LstmSeg)
 
+
+GLUE_NONE, GLUE_SELECT, GLUE_L2BWD = 0, 1, 2   # SGG_GLUE_*
+
+
+class GlueSeg(ctypes.Structure):
+    """SggGlueSeg (include/sgg.h): an L2 glue body riding in an LSTM forward launch."""
+    _fields_ = [("kind", _i), ("pred", _p), ("ldp", _i), ("gt", _p), ("mask", _p), ("ldm", _i), ("scene_off", _p),
+                ("S", _i), ("T", _i), ("B", _i), ("k", _i), ("best", _p), ("w", _f), ("gout", _p), ("dpred", _p),
+                ("ldd", _i), ("term", _p)]
+
 FOLD_MAX = 8   # SGG_FOLD_MAX
 
 
@@ -165,6 +175,7 @@ SIGNATURES = {
     "sgg_lstm_bwd_split": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sgg_lstm_bwd_tail": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sgg_lstm_fwd_seg": (_i, [_sargs, _i, _p]),
+    "sgg_lstm_fwd_seg_glue": (_i, [_sargs, _i, ctypes.POINTER(GlueSeg), _p]),
     "sgg_lstm_fwd_seg2": (_i, [_sargs, _i, _sargs, _i, _p]),
     "sgg_lstm_fwd_seg3": (_i, [_sargs, _i, _sargs, _i, _sargs, _i, _p]),
     "sgg_lstm_bwd_shared": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),

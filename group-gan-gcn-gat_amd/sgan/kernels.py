@@ -481,6 +481,7 @@ def _loss_pending(t):
 
 
 def _take_losses():
+    glue_flush()   # (a queued L2 value sums the terms a held glue segment writes)
     l2, bce, keep = _LOSS["l2"], _LOSS["bce"], _LOSS["keep"]
     _LOSS.update(l2=[], bce=[], keep=[], out=set())
     return l2, bce, keep
@@ -2512,6 +2513,74 @@ def encoder_pair():
         r.flush()
 
 
+# the two per-scene L2 glue launches of a training iteration (sgg_l2_select,
+# sgg_l2_loss_bwd_scenes) ride as extra workgroups of the discriminator
+# encoder's continuation launch that follows them (sgg_lstm_fwd_seg_glue);
+# "0" issues them on their own, as before
+GLUE_RIDE = os.environ.get("SGG_GLUE_RIDE", "1") != "0"
+
+
+class GlueRider:
+    """glue_ride(): K.l2_select and the queued-value K.l2_loss do not launch
+    but hold their glue segment (sgg.h SggGlueSeg); the next saved-state
+    encoder launch of the four-wave family that carries nothing else
+    (_LSTMSeq's `cont` branch continuing a shared prefix, or a whole sequence
+    where no prefix applies -- in the trainer's steps the discriminator's
+    forward, which neither reads what the glue body writes nor fills the
+    device) issues both in one launch (sgg_lstm_fwd_seg_glue).  The
+    glue bodies are the stand-alone kernels' code, so every result has the
+    same bits.  A held segment is issued on its own (flush) when the next LSTM
+    launch is no such carrier, before anything reads its outputs
+    (decoder_init: best; _L2Loss.backward and the queued loss values: dpred,
+    term), when another segment is held, and when the scope closes."""
+
+    def __init__(self):
+        self.held = None   # (SggGlueSeg, its stand-alone launch, the tensors it writes, its HBM bytes)
+
+    def hold(self, seg, alone, outs, nbytes):
+        self.flush()
+        self.held = (seg, alone, outs, nbytes)
+
+    def take(self):
+        """The carrier's call -> (SggGlueSeg, HBM bytes); the carrier's launch owns it from here."""
+        seg, _, _, nb = self.held
+        self.held = None
+        return seg, nb
+
+    def writes(self, t):
+        return self.held is not None and t is not None and any(o.data_ptr() == t.data_ptr() for o in self.held[2])
+
+    def flush(self):
+        if self.held is not None:
+            alone = self.held[1]
+            self.held = None
+            alone()
+
+
+_GRIDE = [None]
+
+
+@contextlib.contextmanager
+def glue_ride():
+    """Scope of a trainer step in which the L2 glue launches may ride with the
+    next shared-prefix continuation launch (GlueRider); outside it nothing is
+    ever held."""
+    prev = _GRIDE[0]
+    r = _GRIDE[0] = GlueRider()
+    try:
+        yield r
+    finally:
+        _GRIDE[0] = prev
+        r.flush()
+
+
+def glue_flush(reader=None):
+    """Issue a held glue segment now: always, or only when it writes `reader`."""
+    r = _GRIDE[0]
+    if r is not None and (reader is None or r.writes(reader)):
+        r.flush()
+
+
 class _LSTMSeq(torch.autograd.Function):
     """Fused LSTM sequence on the raw parameters of Linear(2, E) + LSTM(E, H)
     (+ hidden2pos for the decoder): the embedding fold is one launch
@@ -2539,6 +2608,20 @@ class _LSTMSeq(torch.autograd.Function):
         cont = (pfx is not None and not decoder and h0 is None and c0 is None and not carry
                 and pfx.matches(rel_in, W_hh, T, save))
         ctx.t_sh, ctx.bsrc = (pfx.T_pre, pfx.Bsrc) if cont and pfx.Bsrc < B else (0, 0)
+        # a held L2 glue segment (GlueRider) rides with a saved-state encoder
+        # launch of the four-wave family that carries nothing else: the
+        # discriminator's continuation from the shared prefix or, where the
+        # prefix does not apply (a ped count that is no multiple of 16), its
+        # whole sequence.  Any other LSTM launch is no carrier: the segment
+        # goes first, on its own
+        glue, glue_nb = None, 0.0
+        if _GRIDE[0] is not None and _GRIDE[0].held is not None:
+            if cont or (not decoder and not carry and save and T <= 64
+                        and bool(lib.sgg_lstm_u_ok(T, B, H, 0, 1, u[0].shape[0] if u is not None else 16))
+                        and (u is None or _RIDER[0] is None or _RIDER[0].held is None)):
+                glue, glue_nb = _GRIDE[0].take()
+            else:
+                glue_flush()
         if cont:
             h_all, c_all, act = pfx.h_all, pfx.c_all, pfx.act
             pfx.used = True
@@ -2592,8 +2675,19 @@ class _LSTMSeq(torch.autograd.Function):
         elif cont:
             gs = seg(pfx.T_pre, T - pfx.T_pre, pfx.Bsrc)
 
+            if glue is not None:   # + the glue segment's workgroups (both descriptors own their buffers)
+                def launch():
+                    N.check(lib.sgg_lstm_fwd_seg_glue(N.ctypes.byref(gs), H, N.ctypes.byref(glue), N.stream_ptr()),
+                            "sgg_lstm_fwd_seg_glue")
+            else:
+                def launch():
+                    N.check(lib.sgg_lstm_fwd_seg(N.ctypes.byref(gs), H, N.stream_ptr()), "sgg_lstm_fwd_seg")
+        elif u is not None and glue is not None:   # (sgg_lstm_fwd_u's kernel and arguments, + the glue segment)
+            gs = seg(0, T, B)
+
             def launch():
-                N.check(lib.sgg_lstm_fwd_seg(N.ctypes.byref(gs), H, N.stream_ptr()), "sgg_lstm_fwd_seg")
+                N.check(lib.sgg_lstm_fwd_seg_glue(N.ctypes.byref(gs), H, N.ctypes.byref(glue), N.stream_ptr()),
+                        "sgg_lstm_fwd_seg_glue")
         elif u is not None:
             def launch():
                 N.check(lib.sgg_lstm_fwd_u(N.ptr(rel), N.ptr(A), N.ptr(Whh), N.ptr(bias), N.ptr(h0c), N.ptr(c0c), T,
@@ -2604,7 +2698,13 @@ class _LSTMSeq(torch.autograd.Function):
                 N.check(lib.sgg_lstm_fwd(N.ptr(rel), N.ptr(A), N.ptr(Whh), N.ptr(bias), N.ptr(h0c), N.ptr(c0c),
                                          N.ptr(Wpc), N.ptr(bp), T, B, H, int(decoder), N.ptr(h_all), N.ptr(c_all),
                                          N.ptr(act), N.ptr(rel_out), N.stream_ptr()), "sgg_lstm_fwd")
-            dinit = getattr(h0, "_sgg_dinit", None) if (decoder and h0 is not None and c0 is None) else None
+            if glue is not None:   # (the same kernel and arguments through the segment entry, + the glue segment)
+                gs = seg(0, T, B)
+
+                def launch():
+                    N.check(lib.sgg_lstm_fwd_seg_glue(N.ctypes.byref(gs), H, N.ctypes.byref(glue), N.stream_ptr()),
+                            "sgg_lstm_fwd_seg_glue")
+            dinit =getattr(h0, "_sgg_dinit", None) if (decoder and h0 is not None and c0 is None) else None
             if dinit is not None:
                 # the decoder's h0 / rel0 built in the kernel's prologue (one
                 # launch fewer); where no kernel takes it, materialise them first
@@ -2689,6 +2789,7 @@ class _LSTMSeq(torch.autograd.Function):
             nb = 4.0 * (Ts * B * 2 + ((act.numel() + c_all.numel()) * Ts / T + (Ts + 1) * B * H if save else
                                       (0 if no_final else 2 * B * H))
                         + 4 * H * (H + 3) + (T * B * 2 if decoder else 0) + (U.numel() if U is not None else 0))
+            nb += glue_nb   # (a glue segment's bytes; the launch keeps its name and key)
             if carry or (decoder and kname is not None):   # + the prefix: T_pre steps of Bsrc peds, states saved
                 Hp, Tp, Bp = pfx.H, pfx.T_pre, pfx.Bsrc
                 fl += Tp * Bp * (8.0 * Hp * (Hp + 3) + 12.0 * Hp)
@@ -3159,6 +3260,7 @@ class _DecoderInit(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cvec, z, best, first_k, copies, scenes, last_rel, lazy):
         ctx.dy_link = getattr(cvec, "_sgg_copies_link", None)
+        glue_flush(best)   # (a held best-of-k selection is read from here on)
         cvec = _rows(cvec, "ctx")
         B, Dc = cvec.shape
         nz = z.shape[-1] if z is not None else 0
@@ -3228,10 +3330,33 @@ def l2_select(pred, gt, mask, scenes, k):
     """best-of-k sample per scene (train.py:443-464) -> int64 (S,)."""
     best = torch.empty(scenes.S, device=pred.device, dtype=torch.int64)
     pred = _req(pred, "pred").contiguous()
-    N.check(_lib().sgg_l2_select(N.ptr(pred), N.ptr(_req(gt, "gt").contiguous()), N.ptr(mask), mask.stride(0),
-                                 N.ptr(scenes.scene_off), scenes.S, gt.shape[0], scenes.B, int(k), N.ptr(best),
-                                 N.stream_ptr()), "sgg_l2_select")
+    gt = _req(gt, "gt").contiguous()
+    T, k = gt.shape[0], int(k)
+    rider = _GRIDE[0]
+    if GLUE_RIDE and rider is not None and scenes.S > 0 and 1 <= k <= 256:
+        # held for the next continuation launch (GlueRider); the rollout that
+        # wrote pred is already issued, so stream order stays rollout -> carrier
+        so = scenes.scene_off
+        gl = N.GlueSeg(N.GLUE_SELECT, N.ptr(pred), 0, N.ptr(gt), N.ptr(mask), mask.stride(0), N.ptr(so), scenes.S, T,
+                       scenes.B, k, N.ptr(best), 0.0, None, None, 0, None)
+        gl._keep = (pred, gt, mask, so, best)   # (check_ownership: the descriptor owns what it points to)
+        rider.hold(gl, lambda: _l2_select_alone(pred, gt, mask, scenes, k, best), (best,),
+                   4.0 * T * scenes.B * (2 * k + 3) + 8.0 * scenes.S)
+    else:
+        _l2_select_alone(pred, gt, mask, scenes, k, best)
     return best
+
+
+def _l2_select_alone(pred, gt, mask, scenes, k, best):
+    N.check(_lib().sgg_l2_select(N.ptr(pred), N.ptr(gt), N.ptr(mask), mask.stride(0), N.ptr(scenes.scene_off),
+                                 scenes.S, gt.shape[0], scenes.B, k, N.ptr(best), N.stream_ptr()), "sgg_l2_select")
+
+
+def _l2_bwd_scenes_alone(pred, gt, mask, scenes, w, g, dpred, term):
+    T, B = gt.shape[0], gt.shape[1]
+    N.check(_lib().sgg_l2_loss_bwd_scenes(N.ptr(pred), pred.stride(0), N.ptr(gt), N.ptr(mask), mask.stride(0),
+                                          N.ptr(scenes.scene_off), scenes.S, T, B, w, N.ptr(g), N.ptr(dpred), 2 * B,
+                                          N.ptr(term), N.stream_ptr()), "sgg_l2_loss_bwd_scenes")
 
 
 class _L2Loss(torch.autograd.Function):
@@ -3251,6 +3376,21 @@ class _L2Loss(torch.autograd.Function):
             term = torch.empty(max(scenes.S, 1), device=pred.device, dtype=torch.float32)
             _queue_loss("l2", N.L2Job(N.ptr(term), scenes.S, N.ptr(loss)), (term, loss), (loss,))
             msum = None
+            rider = _GRIDE[0]
+            if GLUE_RIDE and rider is not None and scenes.S > 0:
+                # the backward's launch, formed now for the trainer's backward
+                # seed (the constant 1.0 of const(), as BceLink.run_fused does
+                # for the head) and held for the next continuation launch
+                # (GlueRider); the backward confirms the seed it receives
+                seed = const(1.0, pred.device)
+                dpred = torch.empty(T, B, 2, device=pred.device, dtype=torch.float32)
+                pd, so, wf = pred.detach(), scenes.scene_off, float(w)
+                gl = N.GlueSeg(N.GLUE_L2BWD, N.ptr(pd), pd.stride(0), N.ptr(gt), N.ptr(mask), mask.stride(0),
+                               N.ptr(so), scenes.S, T, B, 0, None, wf, N.ptr(seed), N.ptr(dpred), 2 * B, N.ptr(term))
+                gl._keep = (pd, gt, mask, so, seed, dpred, term)   # (check_ownership)
+                rider.hold(gl, lambda: _l2_bwd_scenes_alone(pd, gt, mask, scenes, wf, seed, dpred, term),
+                           (dpred, term), 4.0 * (T * B * 12 + scenes.S))
+                ctx.glue = (seed, dpred)
         else:
             msum = torch.empty(scenes.S, device=pred.device, dtype=torch.float32)
             term = torch.empty(scenes.S, device=pred.device, dtype=torch.float32)
@@ -3266,12 +3406,17 @@ class _L2Loss(torch.autograd.Function):
         pred, gt, mask, msum, term = ctx.saved_tensors
         scenes, w = ctx.meta
         T, B = gt.shape[0], gt.shape[1]
-        dpred = torch.empty(T, B, 2, device=pred.device, dtype=torch.float32)
+        glue = getattr(ctx, "glue", None)
+        if glue is not None:
+            seed, dpred = glue
+            glue_flush(dpred)   # (still held -- no carrier came: issued now)
+            if g.data_ptr() == seed.data_ptr():
+                # the forward's glue segment assumed exactly this seed: dpred and term are final
+                return dpred, None, None, None, None
+        else:
+            dpred = torch.empty(T, B, 2, device=pred.device, dtype=torch.float32)
         if msum is None:   # (the value was queued: the scenes' mask sums are formed here)
-            N.check(_lib().sgg_l2_loss_bwd_scenes(N.ptr(pred), pred.stride(0), N.ptr(gt), N.ptr(mask), mask.stride(0),
-                                                  N.ptr(scenes.scene_off), scenes.S, T, B, w, N.ptr(g.contiguous()),
-                                                  N.ptr(dpred), 2 * B, N.ptr(term), N.stream_ptr()),
-                    "sgg_l2_loss_bwd_scenes")
+            _l2_bwd_scenes_alone(pred, gt, mask, scenes, w, g.contiguous(), dpred, term)
         else:
             N.check(_lib().sgg_l2_loss_bwd(N.ptr(pred), pred.stride(0), N.ptr(gt), N.ptr(mask), mask.stride(0),
                                            N.ptr(scenes.ped_scene_i32()), N.ptr(msum), T, B, w,

@@ -220,6 +220,9 @@ class KernelOps:
     shared_prefix = staticmethod(K.shared_prefix)
     traj_ahead = staticmethod(K.traj_ahead)
     decoder_pair = staticmethod(K.decoder_pair)
+    # the two per-scene L2 glue launches ride with the discriminator encoder's
+    # continuation launch that follows them (kernels.GlueRider) inside the steps
+    glue_ride = staticmethod(K.glue_ride)
     # loss ops inside this scope write their values at once (not queued for
     # the finish launch): for values read before the backward
     eager_losses = staticmethod(K.eager_losses)
@@ -297,6 +300,9 @@ class GanTrainer:
         st.enter_context(getattr(self.ops, "handoff", contextlib.nullcontext)())
         if not self._grad_observed():
             st.enter_context(getattr(self.ops, "defer_finish", contextlib.nullcontext)())
+        # (entered last, so left first: a held glue launch is issued before the
+        # finish launch that sums its terms)
+        st.enter_context(getattr(self.ops, "glue_ride", contextlib.nullcontext)())
         return st
 
     def _grad_observed(self):

@@ -978,6 +978,52 @@ int sgg_l2_loss_bwd_scenes(const float* pred, int ldp, const float* gt, const fl
                            const int32_t* scene_off, int S, int T, int B, float w, const float* gout, float* dpred,
                            int ldd, float* term, void* stream);
 
+/* sgg_l2_select or sgg_l2_loss_bwd_scenes as a GLUE SEGMENT of an LSTM forward
+ * launch.  Both are a few microseconds of dependent loads on S workgroups,
+ * and in the training iteration the launch that follows each of them -- the
+ * discriminator encoder's continuation (sgg_lstm_fwd_seg, t0 > 0) -- neither
+ * reads what they write nor fills the device: sgg_lstm_fwd_seg_glue issues
+ * that segment with S more workgroups, LAST in the grid, that run the glue
+ * body (the very code of the stand-alone kernels, hence the same bits) and
+ * return, so the glue work leaves the serial chain and its launch disappears.
+ *   kind  SGG_GLUE_NONE: glue ignored, exactly sgg_lstm_fwd_seg.
+ *         SGG_GLUE_SELECT: sgg_l2_select(pred, gt, mask, ldm, scene_off, S, T,
+ *           B, k, best)  (ldp, w, gout, dpred, ldd, term unused)
+ *         SGG_GLUE_L2BWD: sgg_l2_loss_bwd_scenes(pred, ldp, gt, mask, ldm,
+ *           scene_off, S, T, B, w, gout, dpred, ldd, term)  (k, best unused;
+ *           term may be NULL)
+ *   with the argument rules of those entry points (non-NULL pointers, T >= 1,
+ *   ldm >= T, k in 1 .. 256, ldp, ldd >= 2 B); S = 0 is a plain launch.
+ * T, B, S here are the glue body's (prediction steps, peds, scenes), not the
+ * LSTM segment's.  The glue body must not depend on the segment's outputs nor
+ * the segment on the glue's: the two run concurrently.  Errors as
+ * sgg_lstm_fwd_seg where no four-wave kernel exists for H (callers then issue
+ * the stand-alone launch).  One launch where the S glue workgroups find CUs
+ * that the segment's last round of workgroups leaves idle; where the segment
+ * fills the device they would only lengthen its tail, and the entry point
+ * issues the stand-alone glue launch followed by the plain segment instead
+ * (two launches, the same results). */
+#define SGG_GLUE_NONE 0
+#define SGG_GLUE_SELECT 1
+#define SGG_GLUE_L2BWD 2
+typedef struct {
+  int kind;
+  const float* pred;
+  int ldp;
+  const float* gt;
+  const float* mask;
+  int ldm;
+  const int32_t* scene_off;
+  int S, T, B, k;
+  int64_t* best;
+  float w;
+  const float* gout;
+  float* dpred;
+  int ldd;
+  float* term;
+} SggGlueSeg;
+int sgg_lstm_fwd_seg_glue(const SggLstmSeg* seg, int H, const SggGlueSeg* glue, void* stream);
+
 /* ------------------------------------------------------------------------
  * Device-resident data path (sgan/data/device.py): a split's peds live in
  * HBM as one table of `rec` floats per ped
