@@ -24,6 +24,7 @@
 // from 0, then the 16 phase sums are added in phase order.
 #include <string.h>
 
+#include "bce_body.h"
 #include "sgg_common.h"
 
 namespace sgg {
@@ -136,71 +137,9 @@ __device__ void l2_value(const SggL2Job& d, float* lv) {
   __syncthreads();
 }
 
-__device__ __forceinline__ float bce_term(float x, float y) {   // as loss.hip
-  return fmaxf(x, 0.f) - x * y + logf(1.f + expf(-fabsf(x)));
-}
-
-// a BCE job's inputs, loaded before the L2 jobs run (one round trip for all)
-struct BceIn {
-  float v[8], a, b;
-  int nv;
-};
-__device__ __forceinline__ void bce_load(const SggBceJob& d, BceIn& in) {
-  in.a = *d.ya;
-  in.b = *d.yb;
-  in.nv = d.nvalid ? *d.nvalid : d.n;
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const int i = threadIdx.x + kLossThreads * m;
-    in.v[m] = i < d.n ? d.x[i] : 0.f;
-  }
-}
-
-// *loss = w (mean_{i < split} f(x_i, ya) + mean_{i >= split} f(x_i, yb)) over
-// the first nvalid scores of each half; *total = *loss + addend (addend: an
-// L2 job's value from LDS when it is that job's loss, else *d.addend)
-__device__ void bce_value(const SggBceJob& d, const BceIn& in, float addend, float (*red)[kLossThreads / 64]) {
-  float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const int i = threadIdx.x + kLossThreads * m;
-    const bool live = i < d.split ? i < in.nv : i - d.split < in.nv;
-    if (i < d.n && live) {
-      if (i < d.split) s0 += bce_term(in.v[m], in.a);
-      else s1 += bce_term(in.v[m], in.b);
-    }
-  }
-  for (int i = threadIdx.x + 8 * kLossThreads; i < d.n; i += kLossThreads) {   // past the prefetched scores
-    const bool live = i < d.split ? i < in.nv : i - d.split < in.nv;
-    if (live) {
-      if (i < d.split) s0 += bce_term(d.x[i], in.a);
-      else s1 += bce_term(d.x[i], in.b);
-    }
-  }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = s0;
-    red[1][wave] = s1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < kLossThreads / 64; ++w) {
-      t0 += red[0][w];
-      t1 += red[1][w];
-    }
-    const int c0 = min(d.split, in.nv), c1 = min(d.n - d.split, in.nv);
-    const float m0 = c0 > 0 ? t0 / (float)c0 : 0.f;
-    const float m1 = c1 > 0 ? t1 / (float)c1 : 0.f;
-    const float l = d.w * (m0 + m1);
-    *d.loss = l;
-    if (d.total) *d.total = l + addend;
-  }
-  __syncthreads();
-}
+// the BCE jobs' value: bce_body.h (shared with sgg_bce_fwd's kernel: one order
+// of every sum, the same bits)
+static_assert(kLossThreads == kBceThreads, "the loss workgroup runs bce_value with its own thread count");
 
 __device__ void loss_workgroup(const FinishArgs& a, float (*rpart)[256]) {
   __shared__ float lv[SGG_LOSSJOB_MAX];
