@@ -276,6 +276,11 @@ extern "C" const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save,
   if (h < 0 || B <= 0) return "";
   const bool mw = lstm_mw_ok(H, B);
   const char* tf[2] = {"false", "true"};
+  if (bwd == 2) {   // the encoder's weight-gradient backward given no drel_in ("" where it is not built)
+    if (!mw || decoder || !save || !lstm_mw_bwd_nodx_ok(H)) return "";
+    snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_nodx_kernel<%d>", H);
+    return buf;
+  }
   if (bwd) {
     if (mw) snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_kernel<%d, %s, %s>", H, tf[decoder != 0], tf[save != 0]);
     else if (H <= 32) snprintf(buf, sizeof buf, "sgg::lstm_unit_bwd_kernel<%d>", H);
@@ -413,9 +418,12 @@ extern "C" int sgg_lstm_fwd_seg3(const SggLstmSeg* a, int Ha, const SggLstmSeg* 
 extern "C" int sgg_lstm_bwd_shared(const float* A, const float* Whh, const float* h_all, const float* c_all,
                                    const float* act_all, const float* rel, const float* dh_last, int T, int B, int H,
                                    int t_sh, int Bsrc, float* drel_in, float* wpart, void* stream) {
-  SGG_CHECK_ARG(A && Whh && h_all && c_all && act_all && rel && drel_in, "sgg_lstm_bwd_shared: null pointer");
+  SGG_CHECK_ARG(A && Whh && h_all && c_all && act_all && rel, "sgg_lstm_bwd_shared: null pointer");
   SGG_CHECK_ARG(T >= 1 && B >= 1 && t_sh >= 1 && lstm_mw_ok(H, B),
                 "sgg_lstm_bwd_shared: bad sizes or no four-wave kernel (T=%d B=%d H=%d t_sh=%d)", T, B, H, t_sh);
+  SGG_CHECK_ARG(drel_in || (wpart && lstm_mw_bwd_nodx_ok(H)),
+                "sgg_lstm_bwd_shared: drel_in may be NULL only with weight gradients (wpart) and H = 16 / 32 / 48 "
+                "(wpart=%d H=%d)", wpart != nullptr, H);
   return lstm_mw_bwd(A, Whh, nullptr, h_all, c_all, act_all, rel, nullptr, dh_last, nullptr, T, B, H, 0, nullptr,
                      drel_in, nullptr, wpart, (hipStream_t)stream, nullptr, 0, 0, t_sh, Bsrc);
 }
@@ -527,7 +535,10 @@ extern "C" int sgg_lstm_bwd(const float* A, const float* Whh, const float* Wp, c
                             const float* act_all, const float* rel, const float* rel_out, const float* dh_last,
                             const float* dout, int T, int B, int H, int decoder, float* dG, float* dh0,
                             float* drel_in, float* drel_tot, float* wpart, void* stream) {
-  SGG_CHECK_ARG(A && Whh && c_all && act_all && drel_in, "sgg_lstm_bwd: null pointer");
+  SGG_CHECK_ARG(A && Whh && c_all && act_all, "sgg_lstm_bwd: null pointer");
+  SGG_CHECK_ARG(drel_in || (!decoder && wpart && lstm_mw_ok(H, B) && lstm_mw_bwd_nodx_ok(H)),
+                "sgg_lstm_bwd: drel_in may be NULL only for an encoder of the four-wave family with weight gradients "
+                "(wpart) and H = 16 / 32 / 48 (decoder=%d wpart=%d H=%d)", decoder, wpart != nullptr, H);
   SGG_CHECK_ARG(!decoder || (Wp && dout && drel_tot), "sgg_lstm_bwd: decoder needs Wp, dout, drel_tot");
   SGG_CHECK_ARG(T >= 1 && B >= 0, "sgg_lstm_bwd: bad sizes");
   if (B == 0) return 0;

@@ -801,15 +801,27 @@ __global__ void __launch_bounds__(kMwThreads) lstm_mw_fwd3_kernel(MwSeg a, MwSeg
 #ifndef SGG_MW_BWD_X3
 #define SGG_MW_BWD_X3 1
 #endif
+// two operand sets for the owners of the encoder's weight-gradient form
+// without drel_in (kDB below; 0: one set, A/B builds)
+#ifndef SGG_MW_BWD_DB_NODX
+#define SGG_MW_BWD_DB_NODX 1
+#endif
 
-template <int H, bool DEC, bool WGRAD>
-__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_kernel(
+// NODX (encoder with weight gradients only): the input gradient drel_in is
+// not wanted -- the input is data, or comes from a no-grad rollout -- and
+// everything that forms it is left out at compile time: the helpers' A^T dG
+// partials, their shuffles and LDS exchange, the store, and the closing
+// barrier of both wave groups.  The slab and dh0 are bit-identical to the
+// form with drel_in (nothing that feeds them changes).
+template <int H, bool DEC, bool WGRAD, bool NODX>
+__device__ __forceinline__ void mw_bwd_body(
     const float* __restrict__ A, const float* __restrict__ Whh, const float* __restrict__ Wp,
     const float* __restrict__ h_all, const float* __restrict__ c_tile, const float* __restrict__ act_tile,
     const float* __restrict__ rel, const float* __restrict__ rel_out, const float* __restrict__ dh_last,
     const float* __restrict__ dout, int T, int B, float* __restrict__ dh0, float* __restrict__ drel_in,
     float* __restrict__ drel_tot, float* __restrict__ wpart, const float* __restrict__ dout2, int bsplit,
     int t_stop, int t_sh, int Bsrc) {
+  static_assert(!NODX || (WGRAD && !DEC), "NODX: the encoder's weight-gradient form only");
   constexpr int MU = MwCfg<H>::MU, KS = MwCfg<H>::KS, G4 = MwCfg<H>::G4, HP = MwCfg<H>::HP;
   constexpr bool decoder = DEC, wgrad = WGRAD;
   constexpr bool BX3 = SGG_MW_BWD_X3 != 0;   // dh_{t-1} partials on split-bf16 MFMAs (below)
@@ -817,13 +829,14 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
   // (hsum below), and for the encoder drel_in too, so the owners' step is the
   // recurrence alone (the decoder's owners keep drel_in: their dWp / dbp
   // accumulators read it the next step)
-  constexpr bool hacc = wgrad && !decoder;   // helpers: drel_in
-  constexpr bool hdb = wgrad;                 // helpers: db, dA
+  constexpr bool hacc = wgrad && !decoder && !NODX;   // helpers: drel_in
+  constexpr bool oacc = !(wgrad && !decoder);         // owners: drel_in
+  constexpr bool hdb = wgrad;                          // helpers: db, dA
   // decoder slab rows carry [dWp (2 x H) | dbp (2)] after [dW_hh | db | dA]
   constexpr int NHS = MwCfg<H>::NHS, P0 = MwCfg<H>::P, P = P0 + (DEC ? 2 * H + 2 : 0);
   __shared__ float dgb[2][4][KS][kDgPitch];
   __shared__ float part[2][4][KS][64];
-  __shared__ float2 fbp[2][4][kMwPeds];
+  __shared__ float2 fbp[NODX ? 1 : 2][4][kMwPeds];   // (NODX: not used)
   __shared__ float hs[2][kMwPeds][HP];
   const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -1088,7 +1101,7 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
     float v[MU];
     __device__ float operator[](int i) const { return v[i]; }
   };
-  constexpr bool kDB = SGG_MW_BWD_DB && !(WGRAD && !DEC);
+  constexpr bool kDB = SGG_MW_BWD_DB && ((NODX && SGG_MW_BWD_DB_NODX != 0) || !(WGRAD && !DEC));
   typedef typename std::conditional<kDB, fvmu, FArr>::type CellV;
   struct StepIn {
     floatx4 a[MU];
@@ -1150,7 +1163,9 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
   // the encoders' weight gradients the helpers are, and the owners' earlier
   // start only took issue slots from them -- H = 48: 38.5 -> 42.8 us; the
   // G-step's H = 48 input-gradient form 18.0 -> 16.8 us, the decoder's
-  // 19.1 -> 18.7 us)
+  // 19.1 -> 18.7 us.  Without drel_in (NODX) the helpers' step is shorter and
+  // two sets pay again: H = 48 [20, 2560] 37.8 -> 36.9 us, H = 32 [8, 1280]
+  // 10.9 -> 10.6 us; the same build with drel_in 40.6 -> 42.8 us, one set)
   // the step's loaded operands in two register sets used in turn (the loop
   // runs two steps per iteration): a set is loaded one step ahead and read
   // where it was loaded, no loop-carried copy -- a copy of a fresh load had
@@ -1260,12 +1275,12 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
           }
         }
       }
-      if (!hacc) {
+      if (oacc) {
         f0 = fmaf(aa0[i][3], vv[3], fmaf(aa0[i][2], vv[2], fmaf(aa0[i][1], vv[1], fmaf(aa0[i][0], vv[0], f0))));
         f1 = fmaf(aa1[i][3], vv[3], fmaf(aa1[i][2], vv[2], fmaf(aa1[i][1], vv[1], fmaf(aa1[i][0], vv[0], f1))));
       }
     }
-    if (!hacc) {
+    if (oacc) {
       f0 += __shfl_xor(f0, 16);
       f0 += __shfl_xor(f0, 32);
       f1 += __shfl_xor(f1, 16);
@@ -1283,7 +1298,7 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
     LSUBB(3);
     lds_barrier();
     LSUBB(4);
-    if (!hacc && (pgrad || (g == 0 && q == 0))) {   // drel_in[t] = A^T dG_t; decoder: drel_tot[t] = dout[t] + drel_in[t + 1]
+    if (oacc && (pgrad || (g == 0 && q == 0))) {   // drel_in[t] = A^T dG_t; decoder: drel_tot[t] = dout[t] + drel_in[t + 1]
       const float2 r0 = fbp[cur][0][c16], r1 = fbp[cur][1][c16], r2 = fbp[cur][2][c16], r3 = fbp[cur][3][c16];
       const float sx = (r0.x + r1.x) + (r2.x + r3.x), sy = (r0.y + r1.y) + (r2.y + r3.y);
       if (valid && g == 0 && q == 0) {
@@ -1308,7 +1323,7 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
   }
 
   if (hacc) lds_barrier();   // the helpers' last drel_in partials (helper branch)
-  if (t_stop > 0 && valid && g == 0 && q == 0) {   // the skipped steps' input gradients are defined as zero
+  if (!NODX && t_stop > 0 && valid && g == 0 && q == 0) {   // the skipped steps' input gradients are defined as zero
     for (int t = 0; t < t_stop; ++t) *reinterpret_cast<float2*>(drel_in + ((size_t)t * B + ped) * 2) = make_float2(0.f, 0.f);
   }
   if (dh0 && valid) {   // dh0 = W_hh^T dG_0
@@ -1373,6 +1388,31 @@ __global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_b
   LMARK(62);
 }
 
+#define SGG_MW_BWD_PARAMS                                                                                         \
+  const float *__restrict__ A, const float *__restrict__ Whh, const float *__restrict__ Wp,                      \
+      const float *__restrict__ h_all, const float *__restrict__ c_tile, const float *__restrict__ act_tile,     \
+      const float *__restrict__ rel, const float *__restrict__ rel_out, const float *__restrict__ dh_last,       \
+      const float *__restrict__ dout, int T, int B, float *__restrict__ dh0, float *__restrict__ drel_in,        \
+      float *__restrict__ drel_tot, float *__restrict__ wpart, const float *__restrict__ dout2, int bsplit,      \
+      int t_stop, int t_sh, int Bsrc
+#define SGG_MW_BWD_ARGS                                                                                           \
+  A, Whh, Wp, h_all, c_tile, act_tile, rel, rel_out, dh_last, dout, T, B, dh0, drel_in, drel_tot, wpart, dout2,  \
+      bsplit, t_stop, t_sh, Bsrc
+
+template <int H, bool DEC, bool WGRAD>
+__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_kernel(SGG_MW_BWD_PARAMS) {
+  mw_bwd_body<H, DEC, WGRAD, false>(SGG_MW_BWD_ARGS);
+}
+
+// the encoder's weight-gradient form without input gradients (drel_in NULL;
+// mw_bwd_body NODX).  Built for the hidden sizes of the reference's encoders
+// (mw_bwd_nodx_built); elsewhere a NULL drel_in stays an argument error.
+template <int H>
+__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_kernel(SGG_MW_BWD_PARAMS) {
+  mw_bwd_body<H, false, true, true>(SGG_MW_BWD_ARGS);
+}
+constexpr bool mw_bwd_nodx_built(int H) { return H == 16 || H == 32 || H == 48; }
+
 // glue (encoder segments only): gl->S glue workgroups after the segment's
 template <int H>
 int launch_seg(const MwSeg& sg, bool decoder, hipStream_t st, const SggGlueSeg* glue = nullptr) {
@@ -1403,6 +1443,9 @@ int launch_bwd(const float* A, const float* Whh, const float* Wp, const float* h
   const int grid = (B + kMwPeds - 1) / kMwPeds;
   auto k = decoder ? (wpart ? lstm_mw_bwd_kernel<H, true, true> : lstm_mw_bwd_kernel<H, true, false>)
                    : (wpart ? lstm_mw_bwd_kernel<H, false, true> : lstm_mw_bwd_kernel<H, false, false>);
+  if constexpr (mw_bwd_nodx_built(H)) {
+    if (!drel_in) k = lstm_mw_bwd_nodx_kernel<H>;   // (lstm_mw_bwd: encoder with wpart only)
+  }
   hipLaunchKernelGGL(k, dim3(grid), dim3(wpart ? 2 * kMwThreads : kMwThreads), 0, st, A, Whh, Wp, h_all, c_all, act_all, rel, rel_out,
                      dh_last, dout, T, B, dh0, drel_in, drel_tot, wpart, dout2, bsplit, t_stop, t_sh, Bsrc);
   SGG_RETURN_LAUNCH("sgg_lstm_bwd");
@@ -1426,6 +1469,8 @@ bool lstm_mw_ok(int H, int B) {
   if (e && strcmp(e, "big") == 0) return H == 48 || H == 64;
   return H == 16 || H == 32 || H == 48 || H == 64;
 }
+
+bool lstm_mw_bwd_nodx_ok(int H) { return mw_bwd_nodx_built(H); }
 
 long long lstm_mw_state_floats(int T, int B, int H, int which) {
   const long long padded = (long long)(B + kMwPeds - 1) / kMwPeds * kMwPeds;
@@ -1524,6 +1569,9 @@ int lstm_mw_bwd(const float* A, const float* Whh, const float* Wp, const float* 
                 hipStream_t st, const float* dout2, int bsplit, int t_stop, int t_sh, int Bsrc) {
   // the helper waves pass one barrier per step of ALL T steps
   SGG_CHECK_ARG(!wpart || t_stop == 0, "sgg_lstm_bwd: weight gradients need every step (t_stop=%d)", t_stop);
+  SGG_CHECK_ARG(drel_in || (!decoder && wpart && lstm_mw_bwd_nodx_ok(H)),
+                "sgg_lstm_bwd: drel_in may be NULL only for an encoder with weight gradients (wpart) and "
+                "H = 16 / 32 / 48 (decoder=%d wpart=%d H=%d)", decoder, wpart != nullptr, H);
   SGG_CHECK_ARG(t_sh == 0 || (!decoder && t_sh < T && Bsrc >= kMwPeds && Bsrc % kMwPeds == 0 && B % Bsrc == 0),
                 "sgg_lstm_bwd: a shared prefix needs an encoder, t_sh < T and Bsrc a multiple of 16 dividing B "
                 "(t_sh=%d T=%d B=%d Bsrc=%d)", t_sh, T, B, Bsrc);

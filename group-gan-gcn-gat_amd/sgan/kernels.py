@@ -2837,7 +2837,12 @@ class _LSTMSeq(torch.autograd.Function):
         PW = P + (2 * H + 2 if decoder else 0)
         wpart = torch.empty(rows, PW, device=dev, dtype=torch.float32) if (wgrad and rows > 0) else None
         dG = torch.empty(T, B, G4, device=dev, dtype=torch.float32) if rows == 0 else None
-        drel_in = torch.empty(T, B, 2, device=dev, dtype=torch.float32)
+        # an encoder whose input needs no gradient (data, or a no-grad rollout):
+        # the weight-gradient kernel without drel_in, where it is built
+        nodx_name = (lib.sgg_lstm_kernel_name(H, B, 0, 1, 2).decode()
+                     if (not decoder and not need[0] and wpart is not None) else "")
+        nodx = nodx_name != ""
+        drel_in = None if nodx else torch.empty(T, B, 2, device=dev, dtype=torch.float32)
         dh0 = torch.empty(B, H, device=dev, dtype=torch.float32) if has_h0 else None
         drel_tot = torch.empty(T, B, 2, device=dev, dtype=torch.float32) if decoder else None
         split = None
@@ -2889,10 +2894,10 @@ class _LSTMSeq(torch.autograd.Function):
             # weight gradient 2 4H (H + 3); bytes: saved states read, input
             # gradients written, dG or the slab written
             fl = T * B * (8.0 * H * H + 30.0 * H + (8.0 * H * (H + 3) if wpart is not None else 0.0))
-            nb = 4.0 * (act.numel() + c_all.numel() + T * B * 2 + (B * H if has_h0 else 0)
+            nb = 4.0 * (act.numel() + c_all.numel() + (0 if nodx else T * B * 2) + (B * H if has_h0 else 0)
                         + ((T * B * (H + 2) + wpart.numel()) if wpart is not None else 0)
                         + (dG.numel() if dG is not None else 0) + (T * B * 4 if decoder else 0))
-            timer.add(lib.sgg_lstm_kernel_name(H, B, int(decoder), int(wpart is not None), 1).decode(),
+            timer.add(nodx_name or lib.sgg_lstm_kernel_name(H, B, int(decoder), int(wpart is not None), 1).decode(),
                       (T, B, int(decoder), int(wpart is not None)), fl, nb, launch)
         dW_ih = dW_hh = db_ih = db_hh = dWe = dbe = dWp = dbp = None
         side_ctx = side(wpart, dG, h_all, rel, rel_out, drel_tot, W_ih, We, be) if wgrad or decoder \
@@ -2927,7 +2932,7 @@ class _LSTMSeq(torch.autograd.Function):
         if decoder:
             drel = drel_in[0]
         else:
-            drel = drel_in
+            drel = drel_in   # (None: not wanted, not computed)
         return (drel, dW_ih, dW_hh, db_ih, db_hh, dWe, dbe, (dh0 if has_h0 else None), None, dWp, dbp,
                 None, None, None, None, None)
 

@@ -625,10 +625,17 @@ int sgg_lstm_fwd_u(const float* rel, const float* A, const float* Whh, const flo
  *    written and the caller forms the outer-product sums (sgg_xtw); wpart
  *    must be NULL.
  * In the dG form dWp / dbp of the decoder are X^T sums of drel_tot and h_all,
- * left to the caller. */
+ * left to the caller.
+ * drel_in may be NULL where the input gradient is not wanted (the input is
+ * data, or comes from a no-grad rollout), for an encoder (decoder = 0) of the
+ * four-wave family with wpart and H = 16 / 32 / 48: the kernel then leaves
+ * out everything that forms it, and the slab and dh0 are bit-identical to the
+ * call with a buffer.  In every other case NULL is SGG_E_ARG (nothing is
+ * launched). */
 int sgg_lstm_wpart_rows(int H, int B);
 /* Name of the kernel sgg_lstm_fwd (bwd = 0; save = act_all != NULL) or
- * sgg_lstm_bwd (bwd = 1) launches for these sizes, as rocprofv3 lists it
+ * sgg_lstm_bwd (bwd = 1; bwd = 2: given drel_in = NULL, "" where that is an
+ * argument error) launches for these sizes, as rocprofv3 lists it
  * (bench.py's per-kernel timing). */
 const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save, int bwd);
 /* The decoder backward (the four-wave family, sgg_lstm_wpart_rows > 0) with
@@ -716,7 +723,8 @@ int sgg_lstm_fwd_dec_seg(const SggDecInit* di, const float* A, const float* Whh,
  * saved once for Bsrc peds (sgg_lstm_fwd_seg with t0 = t_sh): ped p reads the
  * saved states of steps < t_sh (cells and h up to t_sh) of ped p mod Bsrc.
  * Bsrc a multiple of 16 dividing B; results identical to sgg_lstm_bwd on the
- * complete layout. */
+ * complete layout.  drel_in may be NULL under sgg_lstm_bwd's rule (wpart
+ * given, H = 16 / 32 / 48). */
 int sgg_lstm_bwd_shared(const float* A, const float* Whh, const float* h_all, const float* c_all,
                         const float* act_all, const float* rel, const float* dh_last, int T, int B, int H,
                         int t_sh, int Bsrc, float* drel_in, float* wpart, void* stream);

@@ -148,8 +148,13 @@ def lstm_bwd_w(B, T, H, reps=20):
                                            N.ptr(rel), None, N.ptr(dhl), None, T, B, H, 0, None, None,
                                            N.ptr(drel_in), None, N.ptr(wpart), N.stream_ptr()), "lstm_bwd")
     us = timeit(bwd, reps)
-    print("lstm_bwd+w B=%5d T=%2d H=%2d  %7.2f us  (%s)" % (B, T, H, us, os.environ.get("SGG_LIB", "tree")),
-          flush=True)
+    # the form without input gradients (drel_in NULL), where the library has it
+    nodx = lambda: lib.sgg_lstm_bwd(N.ptr(A), N.ptr(Whh), None, N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel),
+                                    None, N.ptr(dhl), None, T, B, H, 0, None, None, None, None, N.ptr(wpart),
+                                    N.stream_ptr())
+    us0 = timeit(nodx, reps) if nodx() == 0 else float("nan")
+    print("lstm_bwd+w B=%5d T=%2d H=%2d  %7.2f us  no drel_in %7.2f us  (%s)" % (
+        B, T, H, us, us0, os.environ.get("SGG_LIB", "tree")), flush=True)
 
 
 def timeit(call, reps=20):
@@ -218,7 +223,7 @@ if __name__ == "__main__":
             run(S, n, 48, 48)
         sys.exit(0)
     if what == "lbwd":    # the discriminator encoder's backward with weight gradients
-        for (B, T, H) in ((2560, 20, 48), (1280, 20, 48), (2560, 12, 32), (8192, 20, 48)):
+        for (B, T, H) in ((2560, 20, 48), (1280, 20, 48), (2560, 12, 32), (1280, 8, 32), (8192, 20, 48)):
             lstm_bwd_w(B, T, H)
         sys.exit(0)
     if what == "lstm":
