@@ -1,8 +1,8 @@
 // Fused LSTM sequences on v_mfma_f32_16x16x4_f32, one workgroup of four
 // waves per 16 peds (Encoder, reference sgan/models.py:62-92; Decoder
 // rollout :142-178).  Same contract as sgg_lstm_fwd / sgg_lstm_bwd
-// (include/sgg.h), dispatched by lstm.hip for the discriminator's H = 48
-// sequences (and every H with SGG_LSTM_MW=all): each step of the recurrence
+// (include/sgg.h), dispatched by lstm.hip for every hidden size and every
+// sequence the batch-MFMA rollout does not take: each step of the recurrence
 // is latency-bound and the per-ped gate GEMM (4H x H) is spread over all four
 // SIMDs of a CU.
 //
@@ -18,7 +18,7 @@
 // hb[.][ks][lane], because W_hh's columns are loaded in that permuted order.
 // ONE barrier per step (hb double-buffered); every LDS access is lane-linear.
 // Decoder: the hidden2pos feedback r_t = Wp h_t + bp into step t+1 is folded
-// into the weights before step 1 (W_hh + A Wp, b' + A bp; lstm_unit.hip), so
+// into the weights before step 1 (W_hh + A Wp, b' + A bp), so
 // r_t is off the critical path: wave partials in LDS, summed by wave 0 after
 // the step's second barrier.
 //
@@ -72,8 +72,8 @@ constexpr int kMwMaxT = 64;       // encoder inputs (all T steps) are staged in 
 constexpr int kDgPitch = 68;      // dG image row pitch: conflict-free for the transposed A-operand read
 
 // v_exp_f32 / v_rcp_f32 forms (~2 ulp), as the other LSTM kernels.
-// s = 1: sigmoid(x); s = 2: tanh(x) = 2 sigmoid(2x) - 1 (the same
-// expressions as lstm_unit.hip's sigm_u / tanh_u).  exp(-s x) is taken as
+// s = 1: sigmoid(x); s = 2: tanh(x) = 2 sigmoid(2x) - 1, one expression for
+// both.  exp(-s x) is taken as
 // v_exp_f32(x * nsl), nsl = -s log2(e): s is a power of two, so nsl is exact
 // and the argument rounds exactly as __expf's (-(s x)) * log2(e) -- the same
 // bits with one multiply less per gate value
@@ -1453,22 +1453,11 @@ int launch_bwd(const float* A, const float* Whh, const float* Wp, const float* h
 
 }  // namespace
 
-// Policy: every H (16 / 32 / 48 / 64).  Measured at the training shapes
-// (tools/lstm_probe.py, profiles/r02_lstm_*): the generator's H = 32 encoder
-// (T 8, B 1280) fwd 10.7 / bwd 18.2 us here vs 11.2 / 18.9 us + two weight-
-// gradient reductions in the unit-per-thread family, its decoder (T 12,
-// B 2560) 17.6 / 25.8 vs 23.1 / 35.6 us + three reductions.  SGG_LSTM_MW=0
-// disables this form, SGG_LSTM_MW=big keeps it to H >= 48 (kernel
-// comparisons, tools/).  The same predicate picks the forward (when it
-// saves states) and the backward, so the tile-native saved layout is always
-// read by the kernel that wrote it.
-bool lstm_mw_ok(int H, int B) {
-  (void)B;
-  const char* e = getenv("SGG_LSTM_MW");
-  if (e && strcmp(e, "0") == 0) return false;
-  if (e && strcmp(e, "big") == 0) return H == 48 || H == 64;
-  return H == 16 || H == 32 || H == 48 || H == 64;
-}
+// The hidden sizes this family is built for: every one the library takes.
+// The entry points (lstm.hip) refuse any other H before a launch; the H
+// switches above have no error arm.  (What it replaced, and the figures:
+// DESIGN.md, "built, measured, removed".)
+bool lstm_mw_ok(int H) { return H == 16 || H == 32 || H == 48 || H == 64; }
 
 bool lstm_mw_bwd_nodx_ok(int H) { return mw_bwd_nodx_built(H); }
 

@@ -74,24 +74,11 @@ __attribute__((visibility("hidden"))) int lstm_fwd_mfma_dec2(const SggDecInit* d
                                                              int H, float* rel_out, float* rel_out2,
                                                              const SggTrajOut* to2, hipStream_t st);
 
-// lstm_unit.hip: unit-per-thread LSTM sequence kernels (one barrier per
-// step), dispatched by sgg_lstm_fwd / sgg_lstm_bwd; internal
-__attribute__((visibility("hidden"))) bool lstm_unit_ok(int H, int decoder);
-__attribute__((visibility("hidden"))) int lstm_unit_fwd(const float* rel, const float* A, const float* Whh,
-                                                        const float* bias, const float* h0, const float* c0,
-                                                        const float* Wp, const float* bp, int T, int B, int H,
-                                                        int decoder, float* h_all, float* c_all, float* act_all,
-                                                        float* rel_out, hipStream_t st);
-__attribute__((visibility("hidden"))) int lstm_unit_bwd(const float* A, const float* Whh, const float* Wp,
-                                                        const float* c_all, const float* act_all, const float* dh_last,
-                                                        const float* dout, int T, int B, int H, int decoder, float* dG,
-                                                        float* dh0, float* drel_in, float* drel_tot, hipStream_t st);
-
 // lstm_mw.hip: MFMA LSTM sequence kernels, one workgroup of four waves (one
 // per gate block) per 16 peds, tile-native saved states, weight gradients
-// accumulated in the backward kernel; dispatched first by sgg_lstm_fwd /
-// _bwd; internal
-__attribute__((visibility("hidden"))) bool lstm_mw_ok(int H, int B);
+// accumulated in the backward kernel; every backward and every forward the
+// rollout above does not take (lstm.hip); internal.  lstm_mw_ok: H is built
+__attribute__((visibility("hidden"))) bool lstm_mw_ok(int H);
 __attribute__((visibility("hidden"))) long long lstm_mw_state_floats(int T, int B, int H, int which);
 __attribute__((visibility("hidden"))) int lstm_mw_wpart_rows(int H, int B);
 __attribute__((visibility("hidden"))) int lstm_mw_fwd(const float* rel, const float* A, const float* Whh,

@@ -2333,11 +2333,10 @@ class SharedPrefix:
         self.T, self.B = int(T), copies * self.Bsrc
         self.H = int(lstm.weight_hh_l0.shape[1])
         self.ran = self.used = False
-        lib = _lib()
         self.ok = (lstm.num_layers == 1 and 0 < self.T_pre < self.T and self.Bsrc > 0
                    and (copies == 1 or self.Bsrc % 16 == 0)
-                   and bool(lib.sgg_lstm_u_ok(self.T, self.B, self.H, 0, 1, 16))
-                   and bool(lib.sgg_lstm_u_ok(self.T_pre, self.Bsrc, self.H, 0, 1, 16)))
+                   and lstm_u_ok(self.T, self.B, self.H, True, 16)
+                   and lstm_u_ok(self.T_pre, self.Bsrc, self.H, True, 16))
 
     def arm(self, rel, H_g):
         """The generator encoder's launch on `rel`: the prefix rides along iff
@@ -2585,11 +2584,10 @@ class _LSTMSeq(torch.autograd.Function):
     """Fused LSTM sequence on the raw parameters of Linear(2, E) + LSTM(E, H)
     (+ hidden2pos for the decoder): the embedding fold is one launch
     (sgg_fold_fwd), the T-step recurrence another; the backward returns
-    the raw parameters' gradients (sgg_fold_bwd maps dA, dbias back).  Where
-    the library accumulates the weight gradients inside the backward kernel
-    (sgg_lstm_wpart_rows > 0) the gate gradients never reach HBM: one slab
-    row per workgroup, summed by sgg_slab_reduce; otherwise dG is written
-    and reduced by sgg_xtw."""
+    the raw parameters' gradients.  The backward kernel accumulates the
+    weight gradients itself, so the gate gradients never reach HBM: one slab
+    row per workgroup (sgg_lstm_wpart_rows of them), summed and mapped back
+    through the fold (dA, dbias -> dW_ih, dWe, dbe) by one GradFinish launch."""
 
     @staticmethod
     def forward(ctx, rel, W_ih, W_hh, b_ih, b_hh, We, be, h0, c0, Wp, bp, decoder, T, save, u=None, slink=None):
@@ -2617,7 +2615,7 @@ class _LSTMSeq(torch.autograd.Function):
         glue, glue_nb = None, 0.0
         if _GRIDE[0] is not None and _GRIDE[0].held is not None:
             if cont or (not decoder and not carry and save and T <= 64
-                        and bool(lib.sgg_lstm_u_ok(T, B, H, 0, 1, u[0].shape[0] if u is not None else 16))
+                        and lstm_u_ok(T, B, H, True, u[0].shape[0] if u is not None else 16)
                         and (u is None or _RIDER[0] is None or _RIDER[0].held is None)):
                 glue, glue_nb = _GRIDE[0].take()
             else:
@@ -2627,7 +2625,7 @@ class _LSTMSeq(torch.autograd.Function):
             pfx.used = True
         else:
             h_all = torch.empty(T + 1, B, H, device=dev, dtype=torch.float32)
-            # saved states in the layout of the kernel family (H, B) picks
+            # saved states in the kernels' tile-native layout (B padded to 16 peds)
             c_all = torch.empty(int(lib.sgg_lstm_state_floats(T, B, H, 1)), device=dev, dtype=torch.float32)
             act = torch.empty(int(lib.sgg_lstm_state_floats(T, B, H, 0)), device=dev, dtype=torch.float32) \
                 if save else None
@@ -2835,8 +2833,7 @@ class _LSTMSeq(torch.autograd.Function):
         P = G4 * H + G4 + 2 * G4
         # the decoder's rows also carry [dWp (2 x H) | dbp (2)] (lstm_mw.hip)
         PW = P + (2 * H + 2 if decoder else 0)
-        wpart = torch.empty(rows, PW, device=dev, dtype=torch.float32) if (wgrad and rows > 0) else None
-        dG = torch.empty(T, B, G4, device=dev, dtype=torch.float32) if rows == 0 else None
+        wpart = torch.empty(rows, PW, device=dev, dtype=torch.float32) if wgrad else None
         # an encoder whose input needs no gradient (data, or a no-grad rollout):
         # the weight-gradient kernel without drel_in, where it is built
         nodx_name = (lib.sgg_lstm_kernel_name(H, B, 0, 1, 2).decode()
@@ -2852,7 +2849,7 @@ class _LSTMSeq(torch.autograd.Function):
                 ga, gb, bsplit, ph = pend
                 if drel_out is None or drel_out.data_ptr() != ph.data_ptr():
                     raise N.NativeError("decoder backward: the split rollout output has another consumer")
-                if rows > 0 and wgrad:   # the four-wave kernel reads the two blocks in place
+                if wgrad:   # the kernel reads the two blocks in place
                     split = (ga, gb, bsplit)
                 else:
                     drel_out = torch.cat([ga, gb], 1)
@@ -2865,7 +2862,7 @@ class _LSTMSeq(torch.autograd.Function):
         else:
             dout = None
             dhl = dh_last.contiguous() if dh_last is not None else None
-        tail = (not decoder and not wgrad and not has_h0 and rows > 0 and 0 < ctx.t_stop < T)
+        tail = (not decoder and not wgrad and not has_h0 and 0 < ctx.t_stop < T)
         if ctx.t_sh > 0:   # steps < t_sh saved once for column p mod bsrc (SharedPrefix)
             def launch():
                 N.check(lib.sgg_lstm_bwd_shared(N.ptr(A), N.ptr(Whh), N.ptr(h_all), N.ptr(c_all), N.ptr(act),
@@ -2886,21 +2883,21 @@ class _LSTMSeq(torch.autograd.Function):
             def launch():
                 N.check(lib.sgg_lstm_bwd(N.ptr(A), N.ptr(Whh), N.ptr(Wp), N.ptr(h_all), N.ptr(c_all), N.ptr(act),
                                          N.ptr(rel), N.ptr(rel_out), N.ptr(dhl), N.ptr(dout), T, B, H, int(decoder),
-                                         N.ptr(dG), N.ptr(dh0), N.ptr(drel_in), N.ptr(drel_tot), N.ptr(wpart),
-                                         N.stream_ptr()), "sgg_lstm_bwd")
+                                         None, N.ptr(dh0), N.ptr(drel_in), N.ptr(drel_tot), N.ptr(wpart),
+                                         N.stream_ptr()), "sgg_lstm_bwd")   # (None: dG, ignored -- sgg.h)
         launch()
         if timer.active:
             # per ped-step: dh = W^T dG 2 4H H, cell gradient ~30 H, in-kernel
             # weight gradient 2 4H (H + 3); bytes: saved states read, input
-            # gradients written, dG or the slab written
+            # gradients written, the slab written
             fl = T * B * (8.0 * H * H + 30.0 * H + (8.0 * H * (H + 3) if wpart is not None else 0.0))
             nb = 4.0 * (act.numel() + c_all.numel() + (0 if nodx else T * B * 2) + (B * H if has_h0 else 0)
                         + ((T * B * (H + 2) + wpart.numel()) if wpart is not None else 0)
-                        + (dG.numel() if dG is not None else 0) + (T * B * 4 if decoder else 0))
+                        + (T * B * 4 if decoder else 0))
             timer.add(nodx_name or lib.sgg_lstm_kernel_name(H, B, int(decoder), int(wpart is not None), 1).decode(),
                       (T, B, int(decoder), int(wpart is not None)), fl, nb, launch)
         dW_ih = dW_hh = db_ih = db_hh = dWe = dbe = dWp = dbp = None
-        side_ctx = side(wpart, dG, h_all, rel, rel_out, drel_tot, W_ih, We, be) if wgrad or decoder \
+        side_ctx = side(wpart, h_all, rel, rel_out, drel_tot, W_ih, We, be) if wgrad or decoder \
             else contextlib.nullcontext()
         with side_ctx:
             need_p = decoder and (need[9] or need[10])
@@ -2922,39 +2919,15 @@ class _LSTMSeq(torch.autograd.Function):
                 dW_ih, dWe, dbe = gf.fold(W_ih, We, be, wpart, rows, PW, G4 * H + G4, wpart, rows, PW, G4 * H,
                                           dbias_copy=db_hh)
                 gf.run()
-            else:
-                if wgrad:
-                    dW_ih, dW_hh, db_ih, db_hh, dWe, dbe = _lstm_wgrads(lib, wpart, rows, P, G4, H, T, B, dG, h_all,
-                                                                        rel, rel_out, decoder, W_ih, We, be, dev)
-                if need_p:
-                    dr = drel_tot.view(T * B, 2)
-                    dWp, dbp = xtw(h_all[1:].reshape(T * B, H), dr, colsum=True, trans_c=True)
+            elif need_p:   # a frozen LSTM under a trainable hidden2pos
+                dr = drel_tot.view(T * B, 2)
+                dWp, dbp = xtw(h_all[1:].reshape(T * B, H), dr, colsum=True, trans_c=True)
         if decoder:
             drel = drel_in[0]
         else:
             drel = drel_in   # (None: not wanted, not computed)
         return (drel, dW_ih, dW_hh, db_ih, db_hh, dWe, dbe, (dh0 if has_h0 else None), None, dWp, dbp,
                 None, None, None, None, None)
-
-
-def _lstm_wgrads(lib, wpart, rows, P, G4, H, T, B, dG, h_all, rel, rel_out, decoder, W_ih, We, be, dev):
-    """dW_ih, dW_hh, db_ih, db_hh, dWe, dbe of an LSTM sequence from the
-    kernel's slab (or from dG for the families that write it)."""
-    if wpart is not None:
-        flat = torch.empty(P, device=dev, dtype=torch.float32)     # [dW_hh | dbias | dA]
-        N.check(lib.sgg_slab_reduce(N.ptr(wpart), rows, P, N.ptr(flat), N.stream_ptr()), "sgg_slab_reduce")
-        dW_hh = flat[:G4 * H].view(G4, H)
-        dbias = flat[G4 * H:G4 * H + G4]
-        dA = flat[G4 * H + G4:].view(G4, 2)
-    else:
-        dGf = dG.view(T * B, G4)
-        # dW_hh = dG^T h_{t-1} (4H x H, transposed reduction), dbias = sum dG
-        dW_hh, dbias = xtw(h_all[:T].reshape(T * B, H), dGf, colsum=True, trans_c=True)
-        rel_in = torch.cat([rel.unsqueeze(0), rel_out[:-1]], 0) if decoder else rel
-        dA = xtw(rel_in.reshape(T * B, 2), dGf, trans_c=True)                   # 4H x 2
-    db_hh = torch.empty_like(dbias)          # two leaves: no shared gradient storage
-    dW_ih, dWe, dbe = fold_bwd(W_ih, We, be, dA, dbias, dbias_copy=db_hh)
-    return dW_ih, dW_hh, dbias, db_hh, dWe, dbe
 
 
 def lstm_u_ok(T, B, H, save, NU):

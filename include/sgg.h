@@ -516,8 +516,8 @@ int sgg_fold_bwd(const float* W, int ldw, int R, int E, const float* We, const f
  *   t >= 1; rel_out[t] = Wp h_t + bp (T x B x 2) is the predicted displacement.
  * H in {16, 32, 48, 64}.  h_all: (T+1) x B x H with index 0 the initial state.
  * act_all (gate activations) and c_all (cells) are the saved states the
- * backward reads, in a layout private to the kernel family the dispatcher
- * picks for (H, B): allocate sgg_lstm_state_floats(T, B, H, 0) floats for
+ * backward reads, in the tile-native layout of the four-wave kernels (B
+ * padded to 16 peds): allocate sgg_lstm_state_floats(T, B, H, 0) floats for
  * act_all and (.., 1) for c_all.  act_all may be NULL (inference: then only
  * h_all[T] is written) and is required by the backward.
  */
@@ -611,24 +611,22 @@ int sgg_lstm_fwd_u(const float* rel, const float* A, const float* Whh, const flo
  * r_t -> step t+1 is included).  Writes drel_in (T x B x 2, dL/dr_t of the
  * step inputs), dh0 (B x H, may be NULL; no gradient is produced for c0)
  * and, for the decoder, drel_tot (T x B x 2, total dL/d rel_out[t]).
- * Weight gradients, two forms:
- *  - sgg_lstm_wpart_rows(H, B) > 0 (the four-wave MFMA family): pass wpart
- *    (rows x (4H*H + 4H + 8H) floats; the decoder's rows are 2H + 2 wider)
- *    and the kernel accumulates, per workgroup, one slab row [dW_hh (4H x H)
- *    | dbias (4H) | dA (4H x 2)] = sum over its peds and all steps of
- *    dG_t^T [h_{t-1} | 1 | r_in(t)] (h_all and rel -- and rel_out for the
- *    decoder, r_in(t) = rel_out[t-1] -- are read for that), followed for the
- *    decoder by [dWp (2 x H) | dbp (2)] = sum of drel_tot[t] [h_{t+1}^T | 1];
- *    sgg_slab_reduce / sgg_grad_finish sum the rows.  wpart = NULL: input
- *    gradients only (frozen weights).  dG is not used (may be NULL).
- *  - otherwise dG (T x B x 4H, gradient of the gate pre-activations) is
- *    written and the caller forms the outer-product sums (sgg_xtw); wpart
- *    must be NULL.
- * In the dG form dWp / dbp of the decoder are X^T sums of drel_tot and h_all,
- * left to the caller.
+ * Weight gradients: pass wpart (sgg_lstm_wpart_rows(H, B) = ceil(B / 16) rows
+ * x (4H*H + 4H + 8H) floats; the decoder's rows are 2H + 2 wider) and the
+ * kernel accumulates, per workgroup, one slab row [dW_hh (4H x H) | dbias
+ * (4H) | dA (4H x 2)] = sum over its peds and all steps of
+ * dG_t^T [h_{t-1} | 1 | r_in(t)] (dG_t: the gradient of the gate
+ * pre-activations, never written out; h_all and rel -- and rel_out for the
+ * decoder, r_in(t) = rel_out[t-1] -- are read for that), followed for the
+ * decoder by [dWp (2 x H) | dbp (2)] = sum of drel_tot[t] [h_{t+1}^T | 1];
+ * sgg_slab_reduce / sgg_grad_finish sum the rows.  wpart = NULL: input
+ * gradients only (frozen weights; dWp / dbp of a decoder are then X^T sums
+ * of drel_tot and h_all, left to the caller).
+ * The dG parameter is ignored and callers pass NULL: it only keeps the
+ * argument list, which many ctypes callers spell out, as it is.
  * drel_in may be NULL where the input gradient is not wanted (the input is
- * data, or comes from a no-grad rollout), for an encoder (decoder = 0) of the
- * four-wave family with wpart and H = 16 / 32 / 48: the kernel then leaves
+ * data, or comes from a no-grad rollout), for an encoder (decoder = 0)
+ * with wpart and H = 16 / 32 / 48: the kernel then leaves
  * out everything that forms it, and the slab and dh0 are bit-identical to the
  * call with a buffer.  In every other case NULL is SGG_E_ARG (nothing is
  * launched). */
@@ -638,7 +636,7 @@ int sgg_lstm_wpart_rows(int H, int B);
  * argument error) launches for these sizes, as rocprofv3 lists it
  * (bench.py's per-kernel timing). */
 const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save, int bwd);
-/* The decoder backward (the four-wave family, sgg_lstm_wpart_rows > 0) with
+/* The decoder backward with
  * the output gradient in two blocks: peds < bsplit from dout (T x bsplit x 2),
  * the rest from dout2 (T x (B - bsplit) x 2) -- the best-of-k step's best and
  * last samples, whose gradients come from the L2 and the adversarial loss,

@@ -254,12 +254,14 @@ def test_glue_ride_step_is_bit_identical(graphed, monkeypatch):
 
 
 def test_glue_is_flushed_without_a_carrier(monkeypatch):
-    """SGG_LSTM_MW=0: no four-wave launch exists, so nothing can carry; every
+    """K.lstm_u_ok answering no (the one predicate for "this encoder launch can
+    carry"): the encoders return no fused projection, the shared prefix is
+    off and the D-encoder launch is no carrier, so nothing can carry; every
     held glue launch is issued on its own and the steps equal the switch-off
     run bitwise.  (The sequential d_step / g_step: step()'s paired plan shares
-    launches of the four-wave family between the steps and does not run
-    without it.)"""
-    monkeypatch.setenv("SGG_LSTM_MW", "0")
+    encoder launches between the steps and does not run without carriers.)"""
+    from sgan import kernels as K
+    monkeypatch.setattr(K, "lstm_u_ok", lambda *a: False)
     calls = _count_alone(monkeypatch)
     res = []
     for ride in (True, False):

@@ -21,7 +21,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # (kernel-name regex, why it may keep scratch)
 ALLOWED = [
-    (r"lstm_unit_(fwd|bwd)_kernel<", "row-per-ped LSTM family, only reachable with the SGG_LSTM_MW=0 A/B switch"),
     (r"lstm_mw_bwd_kernel<64, ", "H = 64 LSTM backward: no reference configuration has a 64-wide LSTM"),
     (r"lstm_mw_bwd_kernel<48, true, ", "a 48-wide DECODER: the reference's decoders are 32 wide (train.py:53)"),
 ]
