@@ -333,6 +333,44 @@ def test_l2_loss_with_another_backward_seed(monkeypatch):
     close(pk.grad, 0.5 * pv.grad.cpu().numpy(), rtol=1e-5, what="l2 loss grad, seed 1")
 
 
+def test_plain_sequence_carries_a_held_glue_segment(monkeypatch):
+    """A saved-state encoder sequence with no prefix and no projection (the
+    trainer steps above reach the carrier through a continuation or a
+    projection launch only) carries a held select segment through the segment
+    entry == the switch off (sgg_l2_select, then sgg_lstm_fwd): best, h_T and
+    every gradient bitwise.  21 peds (a partial tile), 4 + 4 steps, H = 48;
+    riding issues no stand-alone select at all."""
+    from sgan import kernels as K
+    from sgan.scene import SceneIndex
+    calls = _count_alone(monkeypatch)
+    gt, mask, so, pred_k, _ = _glue_inputs()
+    sc = SceneIndex(np.concatenate([[0], np.cumsum(SIZES)]), DEV)
+    pred = pred_k[:, :3 * sum(SIZES)].contiguous()
+    torch.manual_seed(21)
+    emb, lstm = torch.nn.Linear(2, 16).to(DEV), torch.nn.LSTM(16, H).to(DEV)
+    params = list(emb.parameters()) + list(lstm.parameters())
+    rel, dh = torch.randn(8, 21, 2, device=DEV), torch.randn(21, H, device=DEV)
+    res = []
+    for ride in (True, False):
+        monkeypatch.setattr(K, "GLUE_RIDE", ride)
+        calls.update(select=0, l2bwd=0)
+        for p in params:
+            p.grad = None
+        with K.glue_ride() as rider:
+            best = K.l2_select(pred, gt, mask, sc, 3)
+            assert (rider.held is not None) == ride
+            h, _ = K.lstm_sequence(rel, lstm, emb)
+            assert rider.held is None
+        (h * dh).sum().backward()
+        assert calls["select"] == (0 if ride else 1), (ride, calls)
+        res.append([best, h.detach()] + [p.grad.clone() for p in params])
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+    best, h = res[0][:2]
+    assert 0 <= int(best.min()) and int(best.max()) < 3 and float(h.abs().max()) > 0
+    assert all(float(g.abs().max()) > 0 for g in res[0][2:])
+
+
 def test_select_outside_a_scope_launches_at_once(monkeypatch):
     """Outside a trainer scope nothing is ever held."""
     from sgan import kernels as K
