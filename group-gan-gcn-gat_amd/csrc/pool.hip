@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "sgg_common.h"
+#include "pool_common.h"
 
 namespace sgg {
 
@@ -73,12 +74,6 @@ struct PoolSet {
   const int gb_ = (int)blockIdx.x - (two_ ? (g1) : 0);                                  \
   const int gstride = two_ ? (int)gridDim.x - (g1) : (g1);                              \
   const int xb = (gb_ & 7) * (gstride >> 3) + (gb_ >> 3)   /* XCD-aware (pool_fwd_kernel) */
-
-template <int BN>
-struct PoolCfg {
-  static constexpr int NT = (BN + 15) / 16;                      // 16-wide column tiles
-  static constexpr int BNP = NT * 16 + ((NT % 2 == 0) ? 16 : 0); // odd multiple of 16: conflict-free B reads
-};
 
 // UNR: k-steps unrolled per k-tile.  Fully unrolled (16) the LDS operand
 // prefetch is plain register renaming -- no in-step wait for the reads --
@@ -1473,8 +1468,6 @@ static size_t pool_fwd_lds(int max_rows) {
          sizeof(float2) * SGG_POOL_MAX_PEDS + sizeof(unsigned long long) * (size_t)max_rows * BN;
 }
 
-static int device_cus();
-
 // workgroups of one batch's range: a multiple of 8 (XCD-aware order), <= 32768
 static int pool_range(int nchunks) { return nchunks < 32768 ? (nchunks + 7) & ~7 : 32768; }
 
@@ -1522,18 +1515,6 @@ template <int BN>
 static size_t pool_res_lds(int max_n, int max_rows) {
   return sizeof(float) * ((size_t)16 * PoolCfg<BN>::NT * kUP + 2 * kHidden + (size_t)max_n * kUP) +
          sizeof(float2) * (size_t)max_n + sizeof(unsigned long long) * (size_t)max_rows * BN;
-}
-
-static int device_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int d = 0, v = 0;
-    if (hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess)
-      ncu = v > 0 ? v : 256;
-    else
-      ncu = 256;
-  }
-  return ncu;
 }
 
 template <int BN, int GPW>

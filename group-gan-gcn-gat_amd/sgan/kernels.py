@@ -1214,8 +1214,8 @@ class PoolRider:
     def hold(self, batch, keep, weights, bn, bf16, gpw, nchunks, work, launch):
         self.held = (batch, keep, weights, bn, bf16, gpw, nchunks, work, launch)
 
-    def fits(self, weights, bn, bf16, gpw):
-        if self.held is None:
+    def fits(self, weights, bn, bf16, gpw, wide=False):
+        if self.held is None or wide:    # a wide forward (sgg_pool_fwd_wide) never joins the paired launch
             return False
         _, _, wh, bnh, bfh, gph, _, _, _ = self.held
         return bnh == bn and bfh == bf16 and gph == gpw and all(a is b for a, b in zip(wh, weights))
@@ -1253,6 +1253,17 @@ def pool_pair():
     return _scoped(_PRIDER, PoolRider())
 
 
+def pool_is_wide(scenes):
+    """True when the batch's largest scene is above the LDS-resident pooling
+    kernels' bound: the whole batch then goes through sgg_pool_fwd_wide /
+    sgg_pool_bwd_wide.  Raises (before any launch) above their bound."""
+    from .scene import SGG_POOL_MAX_PEDS, SGG_POOL_WIDE_MAX_PEDS
+    if scenes.max_n > SGG_POOL_WIDE_MAX_PEDS:
+        raise ValueError("social pooling: a scene of %d pedestrians exceeds the bound of %d per scene "
+                         "(SGG_POOL_WIDE_MAX_PEDS)" % (scenes.max_n, SGG_POOL_WIDE_MAX_PEDS))
+    return scenes.max_n > SGG_POOL_MAX_PEDS
+
+
 class _Pool(torch.autograd.Function):
     """PoolHiddenNet on raw parameters: W1 (512 x (E + Hd)) = [W1e | W1h], the
     spatial embedding (We, be), b1, W2 (bn x 512), b2.  Forward: one fold
@@ -1265,6 +1276,9 @@ class _Pool(torch.autograd.Function):
     def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None):
         lib = _lib()
         ctx.link = link
+        # a batch with a scene above the resident kernels' bound: every scene
+        # of it through the tiled (wide) kernels, fp32 in either precision
+        wide = pool_is_wide(scenes)
         h = _rows(h, "h")
         pos = _req(pos, "pos").contiguous()
         B, Hd = h.shape
@@ -1283,43 +1297,52 @@ class _Pool(torch.autograd.Function):
         out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
         am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
         # the opt-in bf16 precision: the 512 -> bn contraction on bf16 MFMA (its own chunk plan)
-        bf16 = _PRECISION == "bf16"
-        fwd = lib.sgg_pool_fwd_bf16 if bf16 else lib.sgg_pool_fwd
-        plan = scenes.pool_plan(bn, bf16=bf16)
+        bf16 = _PRECISION == "bf16" and not wide
+        plan = scenes.pool_plan(bn, wide=True) if wide else scenes.pool_plan(bn, bf16=bf16)
         chunks, nchunks, max_rows, gpw = plan[:4]
         ncd = plan[4] if len(plan) > 4 else None    # a fixed-capacity plan's device chunk count
         if bf16 and ncd is not None:
             gpw = 4   # (a fixed-capacity fp32 plan: its chunks run in passes of up to 512 pairs)
 
-        def launch():
-            N.check(fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(scenes.scene_off),
-                        N.ptr(chunks), nchunks, max_rows, gpw, B, bn, scenes.max_n, N.ptr(out),
-                        N.ptr(am), N.ptr(ncd), N.stream_ptr()), "sgg_pool_fwd")
+        if wide:
+            def launch():
+                N.check(lib.sgg_pool_fwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                              N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
+                                              scenes.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()),
+                        "sgg_pool_fwd_wide")
+            kname = lambda nch: "sgg::pool_fwd_wide_kernel<%d, %d>" % (bn, gpw)
+        else:
+            fwd = lib.sgg_pool_fwd_bf16 if bf16 else lib.sgg_pool_fwd
+
+            def launch():
+                N.check(fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(scenes.scene_off),
+                            N.ptr(chunks), nchunks, max_rows, gpw, B, bn, scenes.max_n, N.ptr(out),
+                            N.ptr(am), N.ptr(ncd), N.stream_ptr()), "sgg_pool_fwd")
+            kname = lambda nch: _pool_kname(bn, gpw, nch, bf16, h.device, scenes.max_n, max_rows)
         nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn     # + the weights, once per launch (_pool_timing)
         work = (scenes.S, B, _pool_flops(scenes, bn), nb)
         rider = _PRIDER[0]
-        if rider is not None and not rider.done and rider.held is None:
+        # (a wide forward is neither held nor carried: it never joins the paired launch)
+        if rider is not None and not wide and not rider.done and rider.held is None:
             # the block's first pooling forward: held until the next one carries it
             batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
                                 gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
             rider.hold(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd), (A, W2, b2), bn, bf16, gpw,
                        nchunks, work, launch)
-        elif rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw):
+        elif rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw, wide=wide):
             batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
                                 gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
             pl, (name, S2, B2, fl2, nb2, nch2) = rider.carry(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd),
                                                              nchunks, work)
             pl()
             if timer.active:
-                timer.add(_pool_kname(bn, gpw, nch2, bf16, h.device, scenes.max_n, max_rows), (S2, B2, "pair"), fl2,
-                          nb2 + _pool_wbytes(bn), pl)
+                timer.add(kname(nch2), (S2, B2, "pair"), fl2, nb2 + _pool_wbytes(bn), pl)
         else:
             if rider is not None:
-                rider.flush()
+                rider.flush()    # a held forward goes out first, on its own
             launch()
             if timer.active:
-                timer.add(_pool_kname(bn, gpw, nchunks, bf16, h.device, scenes.max_n, max_rows), (scenes.S, B), work[2],
-                          nb + _pool_wbytes(bn), launch)
+                timer.add(kname(nchunks), (scenes.S, B), work[2], nb + _pool_wbytes(bn), launch)
         ctx.scenes = scenes
         ctx.E = E
         ctx.save_for_backward(h, pos, W1, We, be, A, W2, U, out, am)
@@ -1338,8 +1361,15 @@ class _Pool(torch.autograd.Function):
         wgrad = any(need[2:8])       # False: weights frozen (the G-step's discriminator), input gradient only
         P = bn * 512 + 1024 + bn
         dU = torch.empty(B, 512, device=h.device, dtype=torch.float32)
-        part = torch.empty(lib.sgg_pool_bwd_grid(sc.S), P, device=h.device, dtype=torch.float32) if wgrad else None
+        wide = pool_is_wide(sc)
+        rows = lib.sgg_pool_bwd_wide_grid(sc.S, sc.max_n) if wide else lib.sgg_pool_bwd_grid(sc.S)
+        part = torch.empty(rows, P, device=h.device, dtype=torch.float32) if wgrad else None
         def launch():
+            if wide:
+                N.check(lib.sgg_pool_bwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                              N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
+                                              N.ptr(part), N.stream_ptr()), "sgg_pool_bwd_wide")
+                return
             N.check(lib.sgg_pool_bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout),
                                      N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU), N.ptr(part),
                                      N.stream_ptr()), "sgg_pool_bwd")
@@ -1348,9 +1378,9 @@ class _Pool(torch.autograd.Function):
             nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * part.numel() if wgrad else 0.0)
             jq = max(1, min(8, 256 // sc.S)) if sc.S >= 1 else 1   # pool.hip pool_bwd_jq / launch_bwd
             stage = (sc.max_n + jq - 1) // jq + 1 <= 16
-            timer.add("sgg::pool_bwd_kernel<%d, %s, %s>" % (bn, "true" if wgrad else "false",
-                                                            "true" if stage else "false"), (sc.S, B),
-                      8.0 * B * bn * 512, nb, launch)
+            name = "sgg::pool_bwd_wide_kernel<%d, %s>" % (bn, "true" if wgrad else "false") if wide else \
+                "sgg::pool_bwd_kernel<%d, %s, %s>" % (bn, "true" if wgrad else "false", "true" if stage else "false")
+            timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
         dh = None
         H = h.shape[1]
         dual = need[0] and wgrad and DUAL_POOL_BWD and not SIDE_STREAM and H <= 64

@@ -714,6 +714,8 @@ class TrajectoryGenerator(nn.Module):
         point, so it runs once per batch and `decode(copies=k)` rolls the k
         samples out (the reference recomputes it k times, bit-identically)."""
         sc = _scenes(seq_start_end, obs_traj.device, scenes)
+        if self.pooling_type:
+            K.pool_is_wide(sc)   # a scene above the pooling bound: ValueError before any launch
         if self.num_layers == 1:
             K.prefold(self.fold_specs())
         U = None
@@ -895,6 +897,9 @@ class TrajectoryDiscriminator(nn.Module):
         return specs
 
     def forward(self, traj, traj_rel, seq_start_end=None, *, scenes=None):
+        if self.d_type != "local":
+            scenes = _scenes(seq_start_end, traj.device, scenes)
+            K.pool_is_wide(scenes)   # a scene above the pooling bound: ValueError before any launch
         if self.encoder.num_layers == 1:   # encoder + pooling folds in one launch (kernels.prefold)
             K.prefold(self.fold_specs())
         if self.d_type != "local" and self.encoder.num_layers == 1 and self.pool_net.fused_ok():

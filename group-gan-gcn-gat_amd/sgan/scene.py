@@ -73,15 +73,21 @@ class SceneIndex:
     # tools/gpu_pool_target.sh; bn 48 keeps 512, where 256 picks 4 groups and
     # loses 2x)
     POOL_TARGET_CHUNKS_SMALL = int(__import__("os").environ.get("SGG_POOL_TARGET_CHUNKS_SMALL", "256"))
+    # the tiled (wide) forward: several workgroups per CU hide its LDS latency
+    # (tools/bench_kernels.py poolwide, [128] x 32 bn 8: 313 us at 256 chunks)
+    POOL_WIDE_TARGET_CHUNKS = int(__import__("os").environ.get("SGG_POOL_WIDE_TARGET_CHUNKS", "2048"))
     POOL_MAX_GPW = int(__import__("os").environ.get("SGG_POOL_MAX_GPW", "0"))
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False):
         """Device chunk table for sgg_pool_fwd (built on the host by
         sgg_pool_plan, cached per bottleneck width); bf16: the table of
-        sgg_pool_fwd_bf16 (sgg_pool_plan_bf16: big chunks, one per CU)."""
-        target_chunks = target_chunks or (self.POOL_TARGET_CHUNKS_SMALL if bn <= 16 else self.POOL_TARGET_CHUNKS)
+        sgg_pool_fwd_bf16 (sgg_pool_plan_bf16: big chunks, one per CU);
+        wide: the table of sgg_pool_fwd_wide (sgg_pool_plan_wide: scenes of
+        up to SGG_POOL_WIDE_MAX_PEDS peds, fp32 only)."""
+        target_chunks = target_chunks or (self.POOL_WIDE_TARGET_CHUNKS if wide else
+                                          self.POOL_TARGET_CHUNKS_SMALL if bn <= 16 else self.POOL_TARGET_CHUNKS)
         plans = self.__dict__.setdefault("_pool_plans", {})
-        key = (bn, target_chunks, self.POOL_MAX_GPW, bool(bf16))
+        key = ("wide", bn, target_chunks) if wide else (bn, target_chunks, self.POOL_MAX_GPW, bool(bf16))
         if key not in plans:
             import ctypes
             lib = N.load()
@@ -89,7 +95,11 @@ class SceneIndex:
             cap = int(self.B) + self.S + 1
             tab = np.zeros((cap, 4), dtype=np.int32)
             mr, gpw = ctypes.c_int(0), ctypes.c_int(0)
-            if bf16:
+            if wide:
+                nc = lib.sgg_pool_plan_wide(off.ctypes.data_as(ctypes.c_void_p), self.S, bn, target_chunks,
+                                            tab.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(mr),
+                                            ctypes.byref(gpw))
+            elif bf16:
                 ncu = torch.cuda.get_device_properties(self.device).multi_processor_count \
                     if torch.device(self.device).type == "cuda" else 256
                 nc = lib.sgg_pool_plan_bf16(off.ctypes.data_as(ctypes.c_void_p), self.S, bn, int(ncu),
@@ -407,6 +417,8 @@ class _PaddedRepeat(SceneIndex):
         raise NotImplementedError("PaddedScenes: the per-op group index is not captured")
 
 
+SGG_POOL_MAX_PEDS = 64          # include/sgg.h: scene bound of the LDS-resident pooling kernels
+SGG_POOL_WIDE_MAX_PEDS = 1024   # include/sgg.h: scene bound of the tiled (wide) pooling kernels
 SGG_POOL_MAX_ROWS = 64   # chunk height bound of sgg_pool_fwd (a padded plan's LDS is sized for it)
 
 

@@ -39,7 +39,10 @@ const char* sgg_last_error(void);
 const char* sgg_source_hash(void);
 
 /* Upper bounds the kernels are built for (checked on every call). */
-#define SGG_POOL_MAX_PEDS 64   /* peds per scene held LDS-resident by the pooling kernel      */
+#define SGG_POOL_MAX_PEDS 64   /* peds per scene of the LDS-resident pooling kernels (sgg_pool_fwd*,
+                                * sgg_pool_bwd); larger scenes take the sgg_pool_*_wide entries    */
+#define SGG_POOL_WIDE_MAX_PEDS 1024  /* peds per scene of the tiled pooling kernels (= the group
+                                      * index's bound)                                             */
 #define SGG_GAT_MAX_NODES 128  /* nodes per segment held LDS-resident by the attention kernel */
 
 /* ------------------------------------------------------------------------
@@ -79,7 +82,7 @@ int sgg_xw_bf16(const float* X, int ldx, const float* Xmask, int ldm, const floa
  * for the backward.
  *   U: B x 512, pos: B x 2, A: 512 x 2, W2: bn x 512 (nn.Linear layout), b2: bn
  *   out: B x bn, argmax: B x bn (int32).  bn in {8, 16, 32, 48, 64}.
- *   max_n = largest scene size in the batch (<= SGG_POOL_MAX_PEDS).
+ *   max_n = largest scene size in the batch (<= SGG_POOL_MAX_PEDS; above: sgg_pool_fwd_wide).
  * Work is split into chunks of whole i-rows of one scene; the chunk table
  * (int32 x 4 per chunk: scene, i0, i1, gpw) is built on the HOST by
  * sgg_pool_plan from the host copy of scene_off and copied to the device by
@@ -165,6 +168,36 @@ int sgg_pool_bwd(const float* U, const float* pos, const float* A, const float* 
                  const float* out, const int32_t* argmax, const float* dout,
                  const int32_t* scene_off, int S, int B, int bn, int max_n,
                  float* dU, float* part, void* stream);
+
+/* Social pooling for batches whose largest scene exceeds SGG_POOL_MAX_PEDS
+ * (max_n up to SGG_POOL_WIDE_MAX_PEDS; smaller batches are accepted too):
+ * the same operands, outputs and argmax contract as sgg_pool_fwd /
+ * sgg_pool_bwd, fp32 only, on kernels that tile the pair space instead of
+ * holding a scene in LDS.
+ * Forward: the chunk table comes from sgg_pool_plan_wide (whole i-rows of one
+ * scene per chunk, <= 64 rows, at least target_chunks chunks where the batch
+ * allows; returns the chunk count, *max_rows and the fixed *gpw of bn -- pass
+ * both on unchanged).  A workgroup walks its chunk against the scene's j in
+ * tiles of 64 peds and in passes of its pair capacity; a pair's value is
+ * computed exactly as sgg_pool_fwd computes it (same FMA chain, same MFMA
+ * order, bias, ReLU), so out and argmax are bitwise sgg_pool_fwd's wherever
+ * both apply.
+ * Backward: work unit = (scene, a range of <= 16 peds j); the unit walks the
+ * scene's i in tiles of 64, ascending.  Writes dU (every row) and one slab row
+ * [dW2 | dA | db2] per workgroup (grid = sgg_pool_bwd_wide_grid(S, max_n)),
+ * summed in a fixed order like sgg_pool_bwd's; part may be NULL (frozen
+ * weights): dU only. */
+int sgg_pool_plan_wide(const int32_t* host_scene_off, int S, int bn, int target_chunks, int32_t* host_chunks,
+                       int cap, int* max_rows, int* gpw);
+int sgg_pool_fwd_wide(const float* U, const float* pos, const float* A, const float* W2,
+                      const float* b2, const int32_t* scene_off, const int32_t* chunks, int nchunks,
+                      int max_rows, int gpw, int B, int bn, int max_n, float* out, int32_t* argmax,
+                      void* stream);
+int sgg_pool_bwd_wide_grid(int S, int max_n);
+int sgg_pool_bwd_wide(const float* U, const float* pos, const float* A, const float* W2,
+                      const float* out, const int32_t* argmax, const float* dout,
+                      const int32_t* scene_off, int S, int B, int bn, int max_n,
+                      float* dU, float* part, void* stream);
 
 /* ------------------------------------------------------------------------
  * Graph attention over the nodes of each segment (GraphAttentionLayer,

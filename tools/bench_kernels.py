@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm]"""
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|...]"""
 import os
 import sys
 
@@ -50,6 +50,52 @@ def run(S, n, hd, bn, gpws=(0,), reps=20):
         us = e0.elapsed_time(e1) / reps * 1e3
         print("pool_fwd S=%5d n=%2d bn=%2d chunks=%5d gpw=%d  %8.1f us  %6.1f TF/s" % (
             S, n, bn, nchunks, g, us, flops / us / 1e6), flush=True)
+
+
+def poolwide(S, n, bn, reps=20):
+    """The tiled pooling forward and backward (sgg_pool_fwd_wide /
+    sgg_pool_bwd_wide) on S scenes of n peds; n <= 64: the resident kernels
+    on the same operands next to them."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B = S * n
+    sc = SceneIndex(np.arange(0, B + 1, n), dev)
+    U = torch.randn(B, 512, device=dev) * 0.3
+    pos = torch.rand(B, 2, device=dev) * 15
+    A = torch.randn(512, 2, device=dev) * 0.3
+    W2 = torch.randn(bn, 512, device=dev) * 0.05
+    b2 = torch.randn(bn, device=dev) * 0.1
+    dout = torch.randn(B, bn, device=dev)
+    lib = N.load()
+    flops = float(S * n * n) * 512 * (4 + 2 * bn)
+    out = torch.empty(B, bn, device=dev)
+    am = torch.empty(B, bn, device=dev, dtype=torch.int32)
+    dU = torch.empty(B, 512, device=dev)
+    P = bn * 512 + 1024 + bn
+    forms = [("wide", True)] + ([("resident", False)] if n <= 64 else [])
+    for name, wide in forms:
+        chunks, nchunks, max_rows, g = sc.pool_plan(bn, wide=wide)
+        if wide:
+            fwd = lambda: N.check(lib.sgg_pool_fwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                                        N.ptr(sc.scene_off), N.ptr(chunks), nchunks, max_rows, g, B,
+                                                        bn, sc.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()), "fwd")
+            part = torch.empty(lib.sgg_pool_bwd_wide_grid(S, n), P, device=dev)
+            bwd = lambda: N.check(lib.sgg_pool_bwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out),
+                                                        N.ptr(am), N.ptr(dout), N.ptr(sc.scene_off), S, B, bn,
+                                                        sc.max_n, N.ptr(dU), N.ptr(part), N.stream_ptr()), "bwd")
+        else:
+            fwd = lambda: N.check(lib.sgg_pool_fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                                   N.ptr(sc.scene_off), N.ptr(chunks), nchunks, max_rows, g, B, bn,
+                                                   sc.max_n, N.ptr(out), N.ptr(am), None, N.stream_ptr()), "fwd")
+            part = torch.empty(lib.sgg_pool_bwd_grid(S), P, device=dev)
+            bwd = lambda: N.check(lib.sgg_pool_bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                                   N.ptr(dout), N.ptr(sc.scene_off), S, B, bn, sc.max_n, N.ptr(dU),
+                                                   N.ptr(part), N.stream_ptr()), "bwd")
+        uf = timeit(fwd, reps)
+        ub = timeit(bwd, reps)
+        print("pool %-8s S=%3d n=%4d bn=%2d chunks=%5d rows=%2d gpw=%d  fwd %8.1f us %6.1f TF/s %5.3f ns/pair  "
+              "bwd %8.1f us" % (name, S, n, bn, nchunks, max_rows, g, uf, flops / uf / 1e6, uf * 1e3 / (S * n * n), ub),
+              flush=True)
 
 
 def lstm(B, T, H, decoder, reps=10, save=False):
@@ -176,6 +222,12 @@ if __name__ == "__main__":
     if what == "dpool":   # the discriminator's pooling (bn 48) at the training shapes
         for (S, n) in ((128, 20), (64, 20), (256, 20), (128, 57)):
             run(S, n, 48, 48)
+        sys.exit(0)
+    if what == "poolwide":   # the tiled pooling kernels above 64 peds, next to the resident ones at 64
+        for bn in (8, 48):
+            # (64 x 128: enough rows for chunks above gpw rows -- several passes per j-tile)
+            for (S, n) in ((64, 64), (32, 128), (8, 256), (1, 1024), (64, 128)):
+                poolwide(S, n, bn)
         sys.exit(0)
     if what == "lbwd":    # the discriminator encoder's backward with weight gradients
         for (B, T, H) in ((2560, 20, 48), (1280, 20, 48), (2560, 12, 32), (1280, 8, 32), (8192, 20, 48)):
