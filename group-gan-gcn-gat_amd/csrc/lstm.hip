@@ -38,7 +38,11 @@ extern "C" const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save,
   static char buf[96];
   if (!lstm_mw_ok(H) || B <= 0) return "";
   const char* tf[2] = {"false", "true"};
-  if (bwd == 2) {   // the encoder's weight-gradient backward given no drel_in ("" where it is not built)
+  if (bwd == 3 || bwd == 4) {   // given a pooled-gradient source (sgg_lstm_bwd_pooldh)
+    if (decoder || !lstm_mw_bwd_pdh_ok(H) || (bwd == 4 && (!save || !lstm_mw_bwd_nodx_ok(H)))) return "";
+    if (bwd == 4) snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_nodx_pdh_kernel<%d>", H);
+    else snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_pdh_kernel<%d, %s>", H, tf[save != 0]);
+  } else if (bwd == 2) {   // the encoder's weight-gradient backward given no drel_in ("" where it is not built)
     if (decoder || !save || !lstm_mw_bwd_nodx_ok(H)) return "";
     snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_nodx_kernel<%d>", H);
   } else if (bwd) {
@@ -178,6 +182,65 @@ extern "C" int sgg_lstm_bwd_shared(const float* A, const float* Whh, const float
                 "(wpart=%d H=%d)", wpart != nullptr, H);
   return lstm_mw_bwd(A, Whh, nullptr, h_all, c_all, act_all, rel, nullptr, dh_last, nullptr, T, B, H, 0, nullptr,
                      drel_in, nullptr, wpart, (hipStream_t)stream, nullptr, 0, 0, t_sh, Bsrc);
+}
+
+extern "C" int sgg_lstm_bwd_pooldh_ok(int H) { return lstm_mw_bwd_pdh_ok(H); }
+
+// Where the prologue pays: the backward's workgroups come in ONE round (16 peds each, <= one per CU).  The launch is
+// then a dependency chain beside idle CUs, and the product's 4 - 5 us in one chain cost less than the 7 - 10 us
+// launch they replace.  A grid of several rounds pays the prologue once per round, while the launch it replaces
+// filled the device: 512 scenes of 20 peds (1,280 and 640 workgroups), +19 us per iteration.
+extern "C" int sgg_lstm_bwd_pooldh_pays(int B, int H) {
+  return B >= 1 && lstm_mw_bwd_pdh_ok(H) && (B + 15) / 16 <= device_cus();
+}
+
+// The h^T dU workgroups ride where the recurrence's workgroups come in ONE round that leaves CUs free, and the
+// riders pass over those free CUs in at most four rounds: a recurrence workgroup is then the launch's long pole
+// (10 - 40 us against a rider's 2 - 3), and the riders are done long before it (the H = 48 forms hold one
+// workgroup per CU, so a rider finds no place beside a recurrence workgroup).  Behind a carrier that fills the
+// device they would be dispatched last and only lengthen its tail (the glue riders' finding,
+// sgg_lstm_fwd_seg_glue): there the partials keep their own launch.
+extern "C" int sgg_lstm_bwd_pooldh_rides(int B, int H, int NU) {
+  if (B < 1 || !lstm_mw_bwd_pdh_ok(H) || NU < 1) return 0;
+  const char* e = getenv("SGG_POOL_DH_RIDE");   // "0": the partials always take their own launch (A/B runs)
+  if (e && e[0] == '0') return 0;
+  const int cus = device_cus(), nblk = (B + 15) / 16;
+  const int riders = ((H + 63) / 64) * ((NU + 63) / 64) * sgg_xtw_splits(B, H, NU);
+  return nblk < cus && riders <= 4 * (cus - nblk);
+}
+
+extern "C" int sgg_lstm_bwd_pooldh(const float* A, const float* Whh, const float* h_all, const float* c_all,
+                                   const float* act_all, const float* rel, const SggPoolDh* src, int T, int B, int H,
+                                   int t_stop, int t_sh, int Bsrc, float* dh0, float* drel_in, float* wpart,
+                                   void* stream) {
+  SGG_CHECK_ARG(A && Whh && h_all && c_all && act_all && rel && src && src->dU && src->W1h,
+                "sgg_lstm_bwd_pooldh: null pointer");
+  SGG_CHECK_ARG(lstm_mw_bwd_pdh_ok(H), "sgg_lstm_bwd_pooldh: no pooled-gradient prologue for H=%d (32 / 48)", H);
+  SGG_CHECK_ARG(T >= 1 && B >= 1 && t_stop >= 0 && t_stop < T && t_sh >= 0, "sgg_lstm_bwd_pooldh: bad sizes T=%d B=%d "
+                "t_stop=%d t_sh=%d", T, B, t_stop, t_sh);
+  SGG_CHECK_ARG(src->NU >= 256 && src->ldu >= src->NU && src->ldw >= H,
+                "sgg_lstm_bwd_pooldh: bad source sizes NU=%d ldu=%d ldw=%d (NU >= 256: sgg_xw's split-K form)", src->NU,
+                src->ldu, src->ldw);
+  SGG_CHECK_ARG(t_stop == 0 || (!wpart && !dh0 && t_sh == 0),
+                "sgg_lstm_bwd_pooldh: t_stop > 0 is the input-gradient form (no wpart, dh0 or shared prefix)");
+  SGG_CHECK_ARG(drel_in || (wpart && lstm_mw_bwd_nodx_ok(H)),
+                "sgg_lstm_bwd_pooldh: drel_in may be NULL only with weight gradients (wpart)");
+  int ride = 0;
+  if (src->ws) {
+    SGG_CHECK_ARG(wpart && src->h && src->ldh >= H, "sgg_lstm_bwd_pooldh: the h^T dU partials need wpart and h");
+    const int splits = sgg_xtw_splits(B, H, src->NU);
+    const size_t need = sizeof(float) * (size_t)splits * ((size_t)H * src->NU + src->NU);
+    SGG_CHECK_ARG(src->splits == splits && src->ws_bytes >= need,
+                  "sgg_lstm_bwd_pooldh: splits %d (sgg_xtw_splits: %d), workspace %zu < %zu bytes", src->splits, splits,
+                  src->ws_bytes, need);
+    ride = sgg_lstm_bwd_pooldh_rides(B, H, src->NU);
+    if (!ride)
+      if (int rc = sgg_xtw_partial(src->h, src->ldh, src->dU, src->ldu, nullptr, 0, B, H, src->NU, 1, src->ws,
+                                   src->ws_bytes, stream))
+        return rc;
+  }
+  return lstm_mw_bwd(A, Whh, nullptr, h_all, c_all, act_all, rel, nullptr, nullptr, nullptr, T, B, H, 0, dh0, drel_in,
+                     nullptr, wpart, (hipStream_t)stream, nullptr, 0, t_stop, t_sh, Bsrc, src, ride);
 }
 
 extern "C" int sgg_lstm_wpart_rows(int H, int B) {

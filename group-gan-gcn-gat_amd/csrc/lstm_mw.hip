@@ -60,6 +60,8 @@
 #include <type_traits>
 
 #include "sgg_common.h"
+#include "xtw_body.h"
+#include "xw_body.h"
 #include "l2_body.h"
 
 namespace sgg {
@@ -813,15 +815,37 @@ __global__ void __launch_bounds__(kMwThreads) lstm_mw_fwd3_kernel(MwSeg a, MwSeg
 // partials, their shuffles and LDS exchange, the store, and the closing
 // barrier of both wave groups.  The slab and dh0 are bit-identical to the
 // form with drel_in (nothing that feeds them changes).
-template <int H, bool DEC, bool WGRAD, bool NODX>
+// PDH (encoder, H = 32 / 48): dh_last is not given; the workgroup forms its
+// 16 x H tile of the pooling backward's dh = dU W1h (+ base) itself, with the
+// instruction sequence of sgg_xw's split-K workgroup (xw_body.h: the same
+// four-way K split, wave w's range, the same LDS sum, then + base), where the
+// value is consumed.  With weight gradients the four helper waves walk K --
+// they have nothing to do before step T - 1 -- while the owners build their
+// weight pieces; in the four-wave form the owners walk it first, before their
+// weight loads.  The four partial tiles lie in LDS (on dgb, which nobody
+// touches before step T - 1, where there are helpers); an owner lane sums its
+// MU elements after barrier (P1), and barrier (P2) lets dgb be written.
+// The workgroups past pd->nblk (weight-gradient forms, pd->ws given) are
+// riders: the split-K partials of dW1h^T = h^T dU and the column sums of dU
+// (xtw_body.h, sgg_xtw_partial's grid flattened), which only the gradient
+// finish reads.
+struct MwPoolDh {
+  SggPoolDh s;
+  int nblk;             // recurrence workgroups; the riders follow
+  int rps, gx, gy;      // riders: rows per split, tiles along H and along NU
+  float* colslab;
+};
+
+template <int H, bool DEC, bool WGRAD, bool NODX, bool PDH = false>
 __device__ __forceinline__ void mw_bwd_body(
     const float* __restrict__ A, const float* __restrict__ Whh, const float* __restrict__ Wp,
     const float* __restrict__ h_all, const float* __restrict__ c_tile, const float* __restrict__ act_tile,
     const float* __restrict__ rel, const float* __restrict__ rel_out, const float* __restrict__ dh_last,
     const float* __restrict__ dout, int T, int B, float* __restrict__ dh0, float* __restrict__ drel_in,
     float* __restrict__ drel_tot, float* __restrict__ wpart, const float* __restrict__ dout2, int bsplit,
-    int t_stop, int t_sh, int Bsrc) {
+    int t_stop, int t_sh, int Bsrc, const MwPoolDh* pd = nullptr) {
   static_assert(!NODX || (WGRAD && !DEC), "NODX: the encoder's weight-gradient form only");
+  static_assert(!PDH || (!DEC && (H == 32 || H == 48)), "PDH: the encoders of the pooling nets (H = 32 / 48)");
   constexpr int MU = MwCfg<H>::MU, KS = MwCfg<H>::KS, G4 = MwCfg<H>::G4, HP = MwCfg<H>::HP;
   constexpr bool decoder = DEC, wgrad = WGRAD;
   constexpr bool BX3 = SGG_MW_BWD_X3 != 0;   // dh_{t-1} partials on split-bf16 MFMAs (below)
@@ -838,6 +862,20 @@ __device__ __forceinline__ void mw_bwd_body(
   __shared__ float part[2][4][KS][64];
   __shared__ float2 fbp[NODX ? 1 : 2][4][kMwPeds];   // (NODX: not used)
   __shared__ float hs[2][kMwPeds][HP];
+  __shared__ float pdhb[PDH && !WGRAD ? kXwSplitLds : 1];   // (four-wave PDH form: no dgb to lie on)
+  static_assert(!PDH || !WGRAD || (sizeof(dgb) >= sizeof(float) * kXwSplitLds && sizeof(dgb) >= sizeof(float) * kXtwRedFloats),
+                "PDH: the product's partial tiles and a rider's reduction lie on dgb");
+  float* const pdh_raw = (PDH && WGRAD) ? &dgb[0][0][0][0] : pdhb;
+  float (*pdh_part)[16][65] = reinterpret_cast<float (*)[16][65]>(pdh_raw);
+  if constexpr (PDH && WGRAD) {
+    if ((int)blockIdx.x >= pd->nblk) {   // a rider (workgroup-uniform): all eight waves pass the body's barriers
+      const int rq = blockIdx.x - pd->nblk, gxy = pd->gx * pd->gy;
+      xtw_partial_body<(H + 15) / 16, 2 * kMwThreads>(pd->s.h, pd->s.ldh, pd->s.dU, pd->s.ldu, nullptr, 0, B, H, pd->s.NU,
+                                                      pd->rps, pd->s.ws, pd->colslab, rq % pd->gx, (rq / pd->gx) % pd->gy,
+                                                      rq / gxy, pdh_raw);
+      return;
+    }
+  }
   const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4, c16 = lane & 15;
@@ -883,6 +921,11 @@ __device__ __forceinline__ void mw_bwd_body(
     // (t)).  dgb[t & 1] is rewritten at step t - 2, after barrier (t - 1),
     // which a helper reaches only once its step-t MFMAs are issued.
     const int hg = g - 4;
+    if constexpr (PDH) {
+      xw_splitk_walk<false>(pd->s.dU, pd->s.ldu, nullptr, 0, pd->s.W1h, pd->s.ldw, B, pd->s.NU, H, blk * kMwPeds, 0, hg,
+                            pdh_part);
+      lds_barrier();   // (P1) the four partial tiles are in LDS
+    }
     floatx4 dw[MU][MU];
 #pragma unroll
     for (int mu = 0; mu < MU; ++mu)
@@ -965,6 +1008,7 @@ __device__ __forceinline__ void mw_bwd_body(
     stage_store((T - 1) & 1);
     if (T >= 2) stage_load(T - 2);
     if (hdb) rel_load(T - 1);
+    if constexpr (PDH) lds_barrier();   // (P2) the owners have read the tiles
     for (int t = T - 1; t >= 0; --t) {
       const int cur = t & 1;
       if (hdb) {
@@ -1026,6 +1070,9 @@ __device__ __forceinline__ void mw_bwd_body(
   // (decoder: the folded W' = W_hh + A Wp for t >= 1, plain W_hh for t = 0 --
   // kept in registers for H <= 32, reloaded at t = 0 above that, where a
   // second copy would spill)
+  if constexpr (PDH && !WGRAD)   // four-wave form: the owners walk K themselves, before their weight loads
+    xw_splitk_walk<false>(pd->s.dU, pd->s.ldu, nullptr, 0, pd->s.W1h, pd->s.ldw, B, pd->s.NU, H, blk * kMwPeds, 0, g,
+                          pdh_part);
   constexpr bool wt0_reg = MU <= 2;
   float wt[MU][MU][4], wt0[MU][MU][4];
 #pragma unroll
@@ -1082,7 +1129,17 @@ __device__ __forceinline__ void mw_bwd_body(
     wp0[i] = decoder ? Wp[u] : 0.f;
     wp1[i] = decoder ? Wp[H + u] : 0.f;
     dc[i] = 0.f;
-    dh[i] = (!decoder && dh_last) ? dh_last[(size_t)pc * H + u] : 0.f;
+    dh[i] = (!PDH && !decoder && dh_last) ? dh_last[(size_t)pc * H + u] : 0.f;
+  }
+  if constexpr (PDH) {
+    float bs[MU];   // the other consumer's gradient of h_T (sgg_xw's accumulate), fetched across the barrier
+#pragma unroll
+    for (int i = 0; i < MU; ++i)
+      bs[i] = pd->s.base ? pd->s.base[(size_t)pc * H + slot_unit(g * MU + i, q)] : 0.f;
+    lds_barrier();   // (P1)
+#pragma unroll
+    for (int i = 0; i < MU; ++i) dh[i] = xw_splitk_sum(pdh_part, c16, slot_unit(g * MU + i, q)) + bs[i];
+    lds_barrier();   // (P2)
   }
 
   // saved activations and cells of the owned slots (and the decoder's output
@@ -1413,6 +1470,20 @@ __global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_kernel(SGG_MW
 }
 constexpr bool mw_bwd_nodx_built(int H) { return H == 16 || H == 32 || H == 48; }
 
+// the encoder forms given a pooled-gradient source (mw_bwd_body PDH): with
+// drel_in (WGRAD: eight waves + riders; else the four-wave input-gradient
+// form, sgg_lstm_bwd_tail's too), and the weight-gradient form without it
+template <int H, bool WGRAD>
+__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_pdh_kernel(SGG_MW_BWD_PARAMS,
+                                                                                              MwPoolDh pd) {
+  mw_bwd_body<H, false, WGRAD, false, true>(SGG_MW_BWD_ARGS, &pd);
+}
+template <int H>
+__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_pdh_kernel(SGG_MW_BWD_PARAMS, MwPoolDh pd) {
+  mw_bwd_body<H, false, true, true, true>(SGG_MW_BWD_ARGS, &pd);
+}
+constexpr bool mw_bwd_pdh_built(int H) { return H == 32 || H == 48; }
+
 // glue (encoder segments only): gl->S glue workgroups after the segment's
 template <int H>
 int launch_seg(const MwSeg& sg, bool decoder, hipStream_t st, const SggGlueSeg* glue = nullptr) {
@@ -1439,8 +1510,27 @@ template <int H>
 int launch_bwd(const float* A, const float* Whh, const float* Wp, const float* h_all, const float* c_all,
                const float* act_all, const float* rel, const float* rel_out, const float* dh_last, const float* dout,
                int T, int B, int decoder, float* dh0, float* drel_in, float* drel_tot, float* wpart, hipStream_t st,
-               const float* dout2, int bsplit, int t_stop, int t_sh, int Bsrc) {
+               const float* dout2, int bsplit, int t_stop, int t_sh, int Bsrc, const SggPoolDh* src, int ride) {
   const int grid = (B + kMwPeds - 1) / kMwPeds;
+  if constexpr (mw_bwd_pdh_built(H)) {
+    if (src) {   // (lstm_mw_bwd: an encoder, no dh_last)
+      MwPoolDh pd{*src, grid, 0, 0, 0, nullptr};
+      int riders = 0;
+      if (ride) {   // sgg_xtw_partial's grid (xtw.hip launch_partial), flattened behind the recurrence workgroups
+        pd.rps = ((B + src->splits - 1) / src->splits + 63) & ~63;
+        pd.gx = (H + 63) / 64;
+        pd.gy = (src->NU + 63) / 64;
+        pd.colslab = src->ws + (size_t)src->splits * H * src->NU;
+        riders = pd.gx * pd.gy * src->splits;
+      }
+      auto kp = wpart ? (drel_in ? lstm_mw_bwd_pdh_kernel<H, true> : lstm_mw_bwd_nodx_pdh_kernel<H>)
+                      : lstm_mw_bwd_pdh_kernel<H, false>;
+      hipLaunchKernelGGL(kp, dim3(grid + riders), dim3(wpart ? 2 * kMwThreads : kMwThreads), 0, st, A, Whh, Wp, h_all,
+                         c_all, act_all, rel, rel_out, dh_last, dout, T, B, dh0, drel_in, drel_tot, wpart, dout2, bsplit,
+                         t_stop, t_sh, Bsrc, pd);
+      SGG_RETURN_LAUNCH("sgg_lstm_bwd_pooldh");
+    }
+  }
   auto k = decoder ? (wpart ? lstm_mw_bwd_kernel<H, true, true> : lstm_mw_bwd_kernel<H, true, false>)
                    : (wpart ? lstm_mw_bwd_kernel<H, false, true> : lstm_mw_bwd_kernel<H, false, false>);
   if constexpr (mw_bwd_nodx_built(H)) {
@@ -1460,6 +1550,8 @@ int launch_bwd(const float* A, const float* Whh, const float* Wp, const float* h
 bool lstm_mw_ok(int H) { return H == 16 || H == 32 || H == 48 || H == 64; }
 
 bool lstm_mw_bwd_nodx_ok(int H) { return mw_bwd_nodx_built(H); }
+
+bool lstm_mw_bwd_pdh_ok(int H) { return mw_bwd_pdh_built(H); }
 
 long long lstm_mw_state_floats(int T, int B, int H, int which) {
   const long long padded = (long long)(B + kMwPeds - 1) / kMwPeds * kMwPeds;
@@ -1555,7 +1647,11 @@ int lstm_mw_fwd_seg3(const MwSeg& a, int Ha, const MwSeg& b, int Hb, const MwSeg
 int lstm_mw_bwd(const float* A, const float* Whh, const float* Wp, const float* h_all, const float* c_all,
                 const float* act_all, const float* rel, const float* rel_out, const float* dh_last, const float* dout,
                 int T, int B, int H, int decoder, float* dh0, float* drel_in, float* drel_tot, float* wpart,
-                hipStream_t st, const float* dout2, int bsplit, int t_stop, int t_sh, int Bsrc) {
+                hipStream_t st, const float* dout2, int bsplit, int t_stop, int t_sh, int Bsrc, const SggPoolDh* src,
+                int ride) {
+  SGG_CHECK_ARG(!src || (!decoder && !dh_last && mw_bwd_pdh_built(H) && (!ride || wpart)),
+                "sgg_lstm_bwd: a pooled-gradient source needs an encoder with H = 32 / 48 and no dh_last; its partials "
+                "ride only with weight gradients (decoder=%d H=%d)", decoder, H);
   // the helper waves pass one barrier per step of ALL T steps
   SGG_CHECK_ARG(!wpart || t_stop == 0, "sgg_lstm_bwd: weight gradients need every step (t_stop=%d)", t_stop);
   SGG_CHECK_ARG(drel_in || (!decoder && wpart && lstm_mw_bwd_nodx_ok(H)),
@@ -1565,10 +1661,10 @@ int lstm_mw_bwd(const float* A, const float* Whh, const float* Wp, const float* 
                 "sgg_lstm_bwd: a shared prefix needs an encoder, t_sh < T and Bsrc a multiple of 16 dividing B "
                 "(t_sh=%d T=%d B=%d Bsrc=%d)", t_sh, T, B, Bsrc);
   switch (H) {
-    case 16: return launch_bwd<16>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc);
-    case 32: return launch_bwd<32>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc);
-    case 48: return launch_bwd<48>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc);
-    default: return launch_bwd<64>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc);
+    case 16: return launch_bwd<16>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc, src, ride);
+    case 32: return launch_bwd<32>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc, src, ride);
+    case 48: return launch_bwd<48>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc, src, ride);
+    default: return launch_bwd<64>(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, decoder, dh0, drel_in, drel_tot, wpart, st, dout2, bsplit, t_stop, t_sh, Bsrc, src, ride);
   }
 }
 

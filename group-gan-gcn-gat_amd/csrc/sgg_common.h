@@ -95,7 +95,10 @@ __attribute__((visibility("hidden"))) int lstm_mw_bwd(const float* A, const floa
                                                       const float* dout, int T, int B, int H, int decoder,
                                                       float* dh0, float* drel_in, float* drel_tot, float* wpart,
                                                       hipStream_t st, const float* dout2 = nullptr,
-                                                      int bsplit = 0, int t_stop = 0, int t_sh = 0, int Bsrc = 0);
+                                                      int bsplit = 0, int t_stop = 0, int t_sh = 0, int Bsrc = 0,
+                                                      const SggPoolDh* src = nullptr, int ride = 0);
+// src (an encoder, dh_last NULL): the hidden sizes the pooled-gradient prologue is built for
+__attribute__((visibility("hidden"))) bool lstm_mw_bwd_pdh_ok(int H);
 // drel_in = NULL (an encoder with wpart): the hidden sizes that form is built for
 __attribute__((visibility("hidden"))) bool lstm_mw_bwd_nodx_ok(int H);
 // one encoder / decoder sequence segment of the four-wave forward (lstm_mw.hip)

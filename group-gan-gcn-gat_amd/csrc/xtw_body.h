@@ -9,12 +9,17 @@ namespace sgg {
 
 constexpr int kXtwRedFloats = 64 * 65 + 64;   // LDS of one workgroup
 
-template <int MT>
+// NT: the threads of the workgroup that runs the body.  256: the four waves
+// above.  512 (a rider of the LSTM backward's launch, lstm_mw.hip): waves
+// 4..7 load, multiply and accumulate nothing, but pass every barrier of the
+// body and share the final stores.
+template <int MT, int NT = 256>
 __device__ __forceinline__ void xtw_partial_body(const float* __restrict__ X, int ldx, const float* __restrict__ Y,
                                                  int ldy, const float* __restrict__ Ym, int ldm, int R, int M, int N,
                                                  int rows_per_split, float* __restrict__ slab,
                                                  float* __restrict__ colslab, int bx, int by, int split,
                                                  float* red /* LDS, kXtwRedFloats */) {
+  static_assert(NT == 256 || NT == 512, "xtw_partial_body: four waves, or four of eight");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c16 = lane & 15, kq = lane >> 4;
   const int m0 = bx * 64;
@@ -60,7 +65,7 @@ __device__ __forceinline__ void xtw_partial_body(const float* __restrict__ X, in
       }
     }
   };
-  const int rw = r0 + 16 * wave;
+  const int rw = (NT == 256 || wave < 4) ? r0 + 16 * wave : r1;   // (an idle wave: an empty row range)
   if (rw < r1) load16(rw, a, b);
   for (int r = rw; r < r1; r += 64) {
     const bool more = r + 64 < r1;
@@ -111,7 +116,7 @@ __device__ __forceinline__ void xtw_partial_body(const float* __restrict__ X, in
     __syncthreads();
   }
   float* out = slab + (size_t)split * M * N;
-  for (int e = threadIdx.x; e < 16 * MT * 64; e += 256) {
+  for (int e = threadIdx.x; e < 16 * MT * 64; e += NT) {
     const int mm = e >> 6, nn = e & 63;
     if (m0 + mm < M && n0 + nn < N) out[(size_t)(m0 + mm) * N + n0 + nn] = red[mm * 65 + nn];
   }

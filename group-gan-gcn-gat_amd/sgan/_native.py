@@ -65,6 +65,12 @@ class LstmSeg(ctypes.Structure):
 _sargs = ctypes.POINTER(LstmSeg)
 
 
+class PoolDh(ctypes.Structure):
+    """SggPoolDh (include/sgg.h): the pooling backward's dU handed to the encoder backward."""
+    _fields_ = [("dU", _p), ("ldu", _i), ("W1h", _p), ("ldw", _i), ("base", _p), ("NU", _i), ("h", _p), ("ldh", _i),
+                ("ws", _p), ("ws_bytes", _sz), ("splits", _i)]
+
+
 GLUE_NONE, GLUE_SELECT, GLUE_L2BWD = 0, 1, 2   # SGG_GLUE_*
 
 
@@ -183,6 +189,11 @@ SIGNATURES = {
     "sgg_lstm_fwd_seg2": (_i, [_sargs, _i, _sargs, _i, _p]),
     "sgg_lstm_fwd_seg3": (_i, [_sargs, _i, _sargs, _i, _sargs, _i, _p]),
     "sgg_lstm_bwd_shared": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sgg_lstm_bwd_pooldh_ok": (_i, [_i]),
+    "sgg_lstm_bwd_pooldh_pays": (_i, [_i, _i]),
+    "sgg_lstm_bwd_pooldh_rides": (_i, [_i, _i, _i]),
+    "sgg_lstm_bwd_pooldh": (_i, [_p, _p, _p, _p, _p, _p, ctypes.POINTER(PoolDh), _i, _i, _i, _i, _i, _i, _p, _p, _p,
+                                 _p]),
     "sgg_lstm_u_ok": (_i, [_i, _i, _i, _i, _i, _i]),
     "sgg_lstm_fwd_u": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p]),
     "sgg_head_ok": (_i, [_i, _i]),

@@ -21,6 +21,10 @@ GATENC_SAVE = os.environ.get("SGG_GATENC_SAVE", "1") != "0"
 # the pooling backward's dh = dU W1h and h^T dU partials in one launch
 # (sgg_pool_dh_dw); "0": two launches (sgg_xw + sgg_xtw_partial)
 DUAL_POOL_BWD = os.environ.get("SGG_DUAL_POOL_BWD", "1") != "0"
+# the pooling backward's dh = dU W1h formed in the prologue of the encoder-LSTM
+# backward that consumes it, the h^T dU partials riding in that launch
+# (sgg_lstm_bwd_pooldh; PoolDhSlot); "0": the launches above
+POOL_DH_IN_LSTM = os.environ.get("SGG_POOL_DH_IN_LSTM", "1") != "0"
 # weight-gradient reductions of the backward on a side stream (needed only by
 # the optimizer step, which joins it).  Off by default: measured slower at
 # configs[1] (61.1k vs 68.9k scenes/s graph-replayed, 12.4k vs 14.8k eager
@@ -1273,9 +1277,10 @@ class _Pool(torch.autograd.Function):
     transposed -> right block)."""
 
     @staticmethod
-    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None):
+    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, pdh=None):
         lib = _lib()
         ctx.link = link
+        ctx.pdh = pdh    # a PoolDhSlot: the backward hands dU to the encoder's backward (social_pool)
         # a batch with a scene above the resident kernels' bound: every scene
         # of it through the tiled (wide) kernels, fp32 in either precision
         wide = pool_is_wide(scenes)
@@ -1384,9 +1389,24 @@ class _Pool(torch.autograd.Function):
         dh = None
         H = h.shape[1]
         dual = need[0] and wgrad and DUAL_POOL_BWD and not SIDE_STREAM and H <= 64
+        # armed (social_pool): neither product is launched here -- the encoder's backward forms dh in its
+        # prologue and carries the h^T dU partials (sgg_lstm_bwd_pooldh); what is returned as the gradient of
+        # h is only the buffer by which that backward recognises its source
+        hand = ctx.pdh is not None and need[0] and not wide and (dual or not wgrad)
         if need[0]:
             base = ctx.link.take() if ctx.link is not None else None
-            if dual:
+            if hand:
+                dh = base if base is not None else torch.empty(B, H, device=h.device, dtype=torch.float32)
+                # the h^T dU partials go along where this backward's finish is queued until the whole backward
+                # pass is over (defer_grad_finish); a finish that runs at once -- its sums may be read by the
+                # next AccumulateGrad -- needs them now: their own launch, below
+                ride = wgrad and _DEFER[0] > 0
+                ws, splits = None, 0
+                if ride:
+                    splits = lib.sgg_xtw_splits(B, H, 512)
+                    ws = torch.empty(splits * (H * 512 + 512), device=h.device, dtype=torch.float32)
+                ctx.pdh.put(dU, W1[:, E:], base, h, ws, splits, dh)
+            elif dual:
                 # dh = dU W1h (+ the other consumer's gradient of h) and the
                 # h^T dU partials (+ column sums) in ONE launch
                 dh = base if base is not None else torch.empty(B, H, device=h.device, dtype=torch.float32)
@@ -1408,13 +1428,13 @@ class _Pool(torch.autograd.Function):
                 # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
                 dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
         if not wgrad:
-            return dh, None, None, None, None, None, None, None, None, None, None
+            return dh, None, None, None, None, None, None, None, None, None, None, None
         with side(part, h, dU, W1, We, be):
             # one launch after the dW1h partials: dW2, db2 (slab [dW2 | dA | db2]
             # row sums), dW1h = dU^T h, dc = sum_j dU_j, and the fold backward
             # of (dA, dc) -> dW1e, dWe, dbe
             rows = part.shape[0]
-            if not dual:
+            if (not dual and not hand) or (hand and ws is None):
                 ws, splits = xtw_partial(h, dU, colsum=True)
             dW1 = torch.empty_like(W1)
             dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
@@ -1426,8 +1446,8 @@ class _Pool(torch.autograd.Function):
             gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
             _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
                                   dW=dW1[:, :E])
-            gf.run()
-        return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None
+            gf.run()   # (with riding partials: queued, issued after the encoder's backward has written them)
+        return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None, None
 
 
 class Handoff:
@@ -1483,12 +1503,80 @@ class GradLink:
         return g
 
 
-def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None):
+class PoolDhSlot:
+    """A one-shot slot from a pooling backward to the backward of the encoder
+    whose final state it pooled: (dU, W1h, base, h, ws, splits, buf).  The
+    pooling backward launches neither dh = dU W1h (+ base) nor the h^T dU
+    partials; the encoder's backward forms dh in its prologue and carries the
+    partials (sgg_lstm_bwd_pooldh).  buf -- base, or an unwritten (B, H)
+    buffer -- is what the pooling backward returns as the gradient of h: it
+    does NOT hold the gradient, and the encoder's backward accepts the slot
+    only if the dh_last it receives is that very buffer.  ws is given only
+    inside defer_grad_finish(): the pooling backward's GradFinish, whose sums
+    read the partials, is then queued until the backward pass is over."""
+
+    def __init__(self):
+        self.pending = None
+
+    def put(self, *args):
+        assert self.pending is None, "PoolDhSlot: a source is already pending"
+        self.pending = args
+        _PDH_OPEN.append(self)
+
+    def take(self):
+        p, self.pending = self.pending, None
+        if p is not None:
+            _PDH_OPEN.remove(self)
+        return p
+
+
+_PDH_OPEN = []
+
+
+def _pooldh_standalone(src):
+    """The stand-alone launches of a taken slot: dh into buf, the partials into ws."""
+    dU, W1h, base, h, ws, splits, buf = src
+    B, H = buf.shape
+    if ws is not None:
+        N.check(_lib().sgg_pool_dh_dw(N.ptr(dU), 512, N.ptr(W1h), W1h.stride(0), N.ptr(buf), buf.stride(0),
+                                      int(base is not None), N.ptr(h), h.stride(0), B, H, N.ptr(ws), ws.numel() * 4,
+                                      N.stream_ptr()), "sgg_pool_dh_dw")
+    else:
+        xw_raw(dU, W1h, None, trans_w=False, prec="fp32", out=buf, act=0 if base is None else 2)
+
+
+def pooldh_check():
+    """Raise if a pooling backward handed its dU over and no encoder backward
+    took it (the buffer it returned as the gradient of h was never filled).
+    The stand-alone products are issued first, so the buffers hold what the
+    switch-off path leaves in them."""
+    if not _PDH_OPEN:
+        return
+    n = len(_PDH_OPEN)
+    for slot in list(_PDH_OPEN):
+        _pooldh_standalone(slot.take())
+    raise RuntimeError("social pooling: %d backward(s) handed dh = dU W1h to an encoder backward that did not run "
+                       "(SGG_POOL_DH_IN_LSTM=0 restores the stand-alone launches)" % n)
+
+
+def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, dh_in_lstm=False):
     """PoolHiddenNet core (models.py:497-549) -> (B, bn); see sgg_pool_fwd.
     link: a GradLink whose pending gradient of h the backward adds to dh.
     U: h W1[:, E:]^T + c when the encoder kernel already produced it
-    (pool_u_spec / lstm_sequence(proj_u=...))."""
-    out, _ = _Pool.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, U)
+    (pool_u_spec / lstm_sequence(proj_u=...)).
+    dh_in_lstm: the caller's statement that this pooling's dh (+ link) is the
+    ONLY gradient reaching the encoder's h_T through autograd; the backward
+    then hands dU to the encoder's backward (PoolDhSlot) where the kernels
+    take it and it pays (sgg_lstm_bwd_pooldh_pays): U from that encoder's
+    epilogue, no wide scene, H = 32 / 48, the peds' workgroups in one round,
+    no side stream."""
+    slot = None
+    if dh_in_lstm and POOL_DH_IN_LSTM and not SIDE_STREAM and U is not None and torch.is_grad_enabled():
+        slot = getattr(U, "_sgg_pdh", None)
+        if slot is not None and (pool_is_wide(scenes)
+                                 or not _lib().sgg_lstm_bwd_pooldh_pays(h.numel() // h.shape[-1], h.shape[-1])):
+            slot = None
+    out, _ = _Pool.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, U, slot)
     return out
 
 
@@ -2677,8 +2765,9 @@ class _LstmEncoder(torch.autograd.Function):
     the next saving "u" launch issues both (_fwd_seg3)."""
 
     @staticmethod
-    def forward(ctx, rel, W_ih, W_hh, b_ih, b_hh, We, be, h0, c0, T, save, u):
+    def forward(ctx, rel, W_ih, W_hh, b_ih, b_hh, We, be, h0, c0, T, save, u, pdh=None):
         lib = _lib()
+        ctx.pdh = pdh   # a PoolDhSlot the pooling net of U may fill in its backward
         ctx.t_stop = int(getattr(rel, "_sgg_grad_from", 0))
         pfx, rider = _PREFIX[0], _RIDER[0]
         rel_in = rel
@@ -2792,7 +2881,34 @@ class _LstmEncoder(torch.autograd.Function):
         drel_in = None if nodx_name else torch.empty(T, B, 2, device=dev, dtype=torch.float32)
         dh0 = torch.empty(B, H, device=dev, dtype=torch.float32) if has_h0 else None
         dhl = dh_last.contiguous() if dh_last is not None else None
-        if ctx.t_sh > 0:   # steps < t_sh saved once for column p mod bsrc (SharedPrefix)
+        # the pooling backward handed its dU over instead of launching dh = dU W1h (PoolDhSlot): dh_last must
+        # be the (unfilled) buffer it returned -- anything else means autograd summed another gradient into it
+        slot = ctx.pdh
+        src = slot.take() if slot is not None else None
+        if src is not None and (dh_last is None or dh_last.data_ptr() != src[6].data_ptr()
+                                or tuple(dh_last.shape[-2:]) != (B, H)):
+            _pooldh_standalone(src)
+            raise RuntimeError("_LstmEncoder.backward: the pooling backward handed dh = dU W1h over, but the final "
+                               "state's gradient is not its buffer -- h_T has a second autograd consumer "
+                               "(do not arm social_pool(dh_in_lstm=True) there)")
+        pname = ""
+        if src is not None:
+            dU, W1h, base, hP, ws, splits, _buf = src
+            tail = ctx.t_sh == 0 and not wgrad and not has_h0 and 0 < ctx.t_stop < T
+            pd = N.PoolDh(N.ptr(dU), dU.stride(0), N.ptr(W1h), W1h.stride(0), N.ptr(base), 512, N.ptr(hP),
+                          hP.stride(0) if hP is not None else 0, N.ptr(ws), ws.numel() * 4 if ws is not None else 0,
+                          splits)
+            pd._keep = src   # (the launch is re-issued by the timer: its buffers live as long as it does)
+            if ws is not None and not wgrad:   # (the pooling net trains under a frozen encoder: its own launch)
+                N.check(lib.sgg_xtw_partial(N.ptr(hP), hP.stride(0), N.ptr(dU), dU.stride(0), None, 0, B, H, 512, 1,
+                                            N.ptr(ws), ws.numel() * 4, N.stream_ptr()), "sgg_xtw_partial")
+                pd.ws = None
+            launch = lambda: N.check(lib.sgg_lstm_bwd_pooldh(
+                N.ptr(A), N.ptr(Whh), N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), N.ctypes.byref(pd), T, B, H,
+                ctx.t_stop if tail else 0, ctx.t_sh, ctx.bsrc, N.ptr(dh0), N.ptr(drel_in), N.ptr(wpart),
+                N.stream_ptr()), "sgg_lstm_bwd_pooldh")
+            pname = lib.sgg_lstm_kernel_name(H, B, 0, int(wgrad), 4 if nodx_name else 3).decode()
+        elif ctx.t_sh > 0:   # steps < t_sh saved once for column p mod bsrc (SharedPrefix)
             launch = lambda: N.check(lib.sgg_lstm_bwd_shared(
                 N.ptr(A), N.ptr(Whh), N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), N.ptr(dhl), T, B, H,
                 ctx.t_sh, ctx.bsrc, N.ptr(drel_in), N.ptr(wpart), N.stream_ptr()), "sgg_lstm_bwd_shared")
@@ -2808,13 +2924,19 @@ class _LstmEncoder(torch.autograd.Function):
         launch()
         if timer.active:
             fl, nb = _lstm_bwd_work(T, B, H, c_all, act, wpart, drel_in is not None, has_h0, False)
-            timer.add(nodx_name or lib.sgg_lstm_kernel_name(H, B, 0, int(wgrad), 1).decode(),
+            if src is not None:
+                # + the product's (and the partials') algorithmic work, in the terms of the launches it replaces
+                # (sgg::xw_xtw_kernel / sgg_xw's records)
+                fl += (4.0 if pd.ws else 2.0) * B * 512 * H
+                nb += 4.0 * (B * 512 + 512 * H + B * H) + ((4.0 * B * 512 + 4.0 * B * H + 4.0 * ws.numel())
+                                                            if pd.ws else 0.0)
+            timer.add(pname or nodx_name or lib.sgg_lstm_kernel_name(H, B, 0, int(wgrad), 1).decode(),
                       (T, B, 0, int(wgrad)), fl, nb, launch)
         grads = (None,) * 6
         if wgrad:
             with side(wpart, h_all, rel, W_ih, We, be):
                 grads = _lstm_finish(wpart, H, W_ih, We, be)
-        return (drel_in,) + grads + (dh0, None, None, None, None)   # (drel_in None: not wanted, not computed)
+        return (drel_in,) + grads + (dh0, None, None, None, None, None)   # (drel_in None: not wanted, not computed)
 
 
 class _LstmDecoder(torch.autograd.Function):
@@ -2998,7 +3120,11 @@ def lstm_sequence(rel, lstm, emb, h0=None, c0=None, proj=None, decoder=False, T=
         return h_last, (rel_out if proj_u is None else None)
     if proj_u is not None and not lstm_u_ok(T, rel.shape[-2], lstm.weight_hh_l0.shape[1], save, proj_u[0].shape[0]):
         proj_u = None
-    h_last, U = _LstmEncoder.apply(*ins, c0, T, save, proj_u)
+    # (the slot by which the pooling net of U may hand its backward's dU to this encoder's backward)
+    pdh = PoolDhSlot() if (proj_u is not None and save and POOL_DH_IN_LSTM) else None
+    h_last, U = _LstmEncoder.apply(*ins, c0, T, save, proj_u, pdh)
+    if pdh is not None:
+        U._sgg_pdh = pdh
     return h_last, (U if proj_u is not None else None)
 
 

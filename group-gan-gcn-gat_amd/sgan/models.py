@@ -209,7 +209,7 @@ class PoolHiddenNet(nn.Module):
     def fused_ok(self):
         return not (self.batch_norm or self.activation != "relu" or self.dropout > 0)
 
-    def forward(self, h_states, seq_start_end, end_pos, scenes=None, link=None, U=None):
+    def forward(self, h_states, seq_start_end, end_pos, scenes=None, link=None, U=None, dh_in_lstm=False):
         """U (optional): h W1[:, E:]^T + c already computed by the encoder
         kernel's epilogue (K.pool_u_spec)."""
         if not self.fused_ok():
@@ -219,7 +219,7 @@ class PoolHiddenNet(nn.Module):
         l1, l2 = self.mlp_pre_pool[0], self.mlp_pre_pool[2]
         emb = self.spatial_embedding
         return K.social_pool(h_states.reshape(-1, self.h_dim), end_pos, l1.weight, emb.weight, emb.bias, l1.bias,
-                             l2.weight, l2.bias, sc, link=link, U=U)
+                             l2.weight, l2.bias, sc, link=link, U=U, dh_in_lstm=dh_in_lstm)
 
 
 # ---------------------------------------------------------------------------
@@ -731,7 +731,14 @@ class TrajectoryGenerator(nn.Module):
             # the GAT encoder's / GCN module's gradient of h reaches the pooling
             # backward, which adds it in its own launch
             link = K.GradLink() if two_block and torch.is_grad_enabled() else None
-            pool_h = self.pool_net(final_encoder_h, seq_start_end, end_pos, scenes=sc, link=link, U=U)
+            # (where the graph module takes the link -- its one-launch path; the per-op path concatenates
+            # [h | pool_h] under autograd -- the pooling's dh is the only gradient autograd carries to the
+            # encoder's h_T, and that encoder's backward may form it: kernels.social_pool dh_in_lstm)
+            sole = link is not None and (
+                self.gatencoder.fused_ok(sc, True) if self.graph == "gat" else
+                self.gcn_module.fused_ok(sc, self.encoder_h_dim + self.pool_net.bottleneck_dim))
+            pool_h = self.pool_net(final_encoder_h, seq_start_end, end_pos, scenes=sc, link=link, U=U,
+                                   dh_in_lstm=sole)
             if two_block:
                 # the graph module reads [h | pool_h] as two blocks (no cat)
                 module = self.gatencoder if self.graph == "gat" else self.gcn_module
@@ -806,7 +813,9 @@ class TrajectoryGenerator(nn.Module):
         with K.pool_pair():
             with torch.no_grad():
                 pool_a = self.pool_net(h_a, sse_a, obs_a[-1], scenes=sc_a, U=U_a)
-            pool_b = self.pool_net(h_b, sse_b, obs_b[-1], scenes=sc_b, link=link, U=U_b)
+            # (pair_ok: the graph module's one-launch path takes the link, so the pooling's dh is the only
+            # gradient autograd carries to h_b -- kernels.social_pool dh_in_lstm)
+            pool_b = self.pool_net(h_b, sse_b, obs_b[-1], scenes=sc_b, link=link, U=U_b, dh_in_lstm=link is not None)
         if self.graph == "sgangat":
             # both batches' batched-GAT layers, then both GCNModules, in
             # shared launches
@@ -910,7 +919,8 @@ class TrajectoryDiscriminator(nn.Module):
         if self.d_type == "local":
             x = final_h.squeeze()
         else:
-            x = self.pool_net(final_h.squeeze(), seq_start_end, traj[0], scenes=scenes, U=U)
+            # (the pooling net is the encoder state's only consumer: kernels.social_pool dh_in_lstm)
+            x = self.pool_net(final_h.squeeze(), seq_start_end, traj[0], scenes=scenes, U=U, dh_in_lstm=True)
         # Linear -> ReLU -> Linear(., 1) -> ReLU in one launch each way
         spec = K.head_ok(self.real_classifier)
         if spec is not None and x.dim() == 2:

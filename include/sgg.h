@@ -667,7 +667,8 @@ int sgg_lstm_wpart_rows(int H, int B);
 /* Name of the kernel sgg_lstm_fwd (bwd = 0; save = act_all != NULL) or
  * sgg_lstm_bwd (bwd = 1; bwd = 2: given drel_in = NULL, "" where that is an
  * argument error) launches for these sizes, as rocprofv3 lists it
- * (bench.py's per-kernel timing). */
+ * (bench.py's per-kernel timing).  bwd = 3 / 4: sgg_lstm_bwd_pooldh's kernel
+ * in the place of bwd = 1 / 2's ("" where it is not built). */
 const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save, int bwd);
 /* The decoder backward with
  * the output gradient in two blocks: peds < bsplit from dout (T x bsplit x 2),
@@ -759,6 +760,50 @@ int sgg_lstm_fwd_dec_seg(const SggDecInit* di, const float* A, const float* Whh,
 int sgg_lstm_bwd_shared(const float* A, const float* Whh, const float* h_all, const float* c_all,
                         const float* act_all, const float* rel, const float* dh_last, int T, int B, int H,
                         int t_sh, int Bsrc, float* drel_in, float* wpart, void* stream);
+
+/* The encoder backward given, in place of a finished dh_last, the pooling
+ * backward's dU: each workgroup forms its 16 peds' rows of
+ *   dh_T = dU W1h (+ base)
+ * in its prologue, bitwise what sgg_xw(dU, W1h, act = base ? 2 : 0) (K = NU >=
+ * 256: the split-K form) or sgg_pool_dh_dw writes -- the same four-way split
+ * of K, the same order of the sum, then + base -- and then runs the backward
+ * that sgg_lstm_bwd / _shared / _tail would run on that dh_last, with
+ * bit-identical results; one launch of the serial chain fewer.
+ *   dU    B x NU, rows ldu apart            W1h   NU x H, rows ldw apart
+ *   base  B x H contiguous, or NULL         NU    512
+ * ws != NULL (weight gradients only: wpart given): the launch also leaves the
+ * split-K partials of h^T dU (h: B x H, rows ldh apart) and the column sums of
+ * dU in ws, laid out exactly as sgg_xtw_partial(h, dU, colsum = 1) lays them
+ * out (splits = sgg_xtw_splits(B, H, NU); ws_bytes >= splits (NU H + NU)
+ * floats).  Their workgroups ride behind the recurrence's in the same grid
+ * where sgg_lstm_bwd_pooldh_rides(B, H, NU) says so; elsewhere the entry
+ * point issues sgg_xtw_partial first (two launches, the same values).
+ * Form: t_sh > 0 as sgg_lstm_bwd_shared (Bsrc); else t_stop > 0 (no wpart,
+ * no dh0) as sgg_lstm_bwd_tail; else sgg_lstm_bwd (decoder = 0; drel_in NULL
+ * under its rule).  Built for H = 32 and 48 (sgg_lstm_bwd_pooldh_ok); any
+ * other H is SGG_E_ARG and nothing is launched: the caller then forms dh_last
+ * with sgg_xw / sgg_pool_dh_dw and calls the plain entry points. */
+typedef struct {
+  const float* dU;
+  int ldu;
+  const float* W1h;
+  int ldw;
+  const float* base;
+  int NU;
+  const float* h;
+  int ldh;
+  float* ws;
+  size_t ws_bytes;
+  int splits;
+} SggPoolDh;
+int sgg_lstm_bwd_pooldh_ok(int H);
+/* the caller's rule for handing dU over: built for H, and the B peds' workgroups come in one round (<= one per CU);
+ * a grid of several rounds pays the prologue once per round and keeps the stand-alone launches */
+int sgg_lstm_bwd_pooldh_pays(int B, int H);
+int sgg_lstm_bwd_pooldh_rides(int B, int H, int NU);
+int sgg_lstm_bwd_pooldh(const float* A, const float* Whh, const float* h_all, const float* c_all,
+                        const float* act_all, const float* rel, const SggPoolDh* src, int T, int B, int H, int t_stop,
+                        int t_sh, int Bsrc, float* dh0, float* drel_in, float* wpart, void* stream);
 
 /* ------------------------------------------------------------------------
  * Adversarial loss (losses.py:5-21 bce_loss; gan_d_loss :36-49 sums two of
