@@ -16,7 +16,7 @@
 // grid runs over (segment, head) pairs; head h writes columns [hF, hF + F) of
 // y, so the concatenation of heads (GAT.py:86) is free.  `bias` (F, shared by
 // the heads, GAT.py:41) is added to the aggregate before the epilogue.
-#include "sgg_common.h"
+#include "gat_common.h"
 
 namespace sgg {
 
@@ -29,55 +29,7 @@ __device__ long long g_gat_prof[64];
 #define GPMARK(i)
 #endif
 
-constexpr int kGatThreads = 256;
-constexpr int kGatWaves = kGatThreads / 64;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float lrelu(float x, float alpha) { return x > 0.f ? x : alpha * x; }
-
-// LDS row stride of a staged node tile: F rounded up to the 4-feature MFMA
-// k-step (the pad columns hold zeros), odd
-__host__ __device__ __forceinline__ int gat_fs(int F) { return ((F + 3) & ~3) | 1; }
-__host__ __device__ __forceinline__ int gat_r16(int n) { return (n + 15) & ~15; }
-
-// A rows x cols block into LDS with 16 loads in flight per thread (a loop
-// of one load and one store per element waits a memory latency per
-// element): ld(r, c) is called with indices clamped into [0, nv) x [0, cv)
-// and its value masked to zero outside; st(r, c, v) stores it
-template <typename Ld, typename St>
-__device__ __forceinline__ void stage_block(int rows, int cols, int nv, int cv, Ld ld, St st) {
-  constexpr int kU = 16;
-  const int total = rows * cols;
-  const int dq = kGatThreads / cols, dr = kGatThreads - dq * cols;   // one step of kGatThreads elements
-  for (int base = 0; base < total; base += kU * kGatThreads) {
-    const int e0 = base + (int)threadIdx.x;
-    const int r0 = e0 / cols, c0 = e0 - r0 * cols;
-    float v[kU];
-    int r = r0, c = c0;
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {   // (slots past the block load a clamped element: no branch)
-      v[u] = keep_if(ld(min(r, nv - 1), min(c, cv - 1)), r < nv && c < cv);
-      r += dq;
-      c += dr;
-      if (c >= cols) {
-        c -= cols;
-        ++r;
-      }
-    }
-    r = r0;
-    c = c0;
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      if (e0 + u * kGatThreads < total) st(r, c, v[u]);
-      r += dq;
-      c += dr;
-      if (c >= cols) {
-        c -= cols;
-        ++r;
-      }
-    }
-  }
-}
 
 // Both kernels work on 16 x 16 x 4 fp32 MFMA tiles (exact fp32 products;
 // v_mfma_f32_16x16x4_f32: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][c
@@ -88,40 +40,6 @@ __device__ __forceinline__ void stage_block(int rows, int cols, int nv, int cv, 
 // operand layout (lane = row i, k-step m = nodes 4m + (lane >> 4)), so the
 // softmax needs two cross-lane steps per reduction and the aggregation
 // att @ Wh reads only Wh (LDS) -- no attention matrix is stored.
-
-// s_i = Wh_i . a_src, t_i = Wh_i . a_dst (a_s / a_d: LDS copies) and the
-// labels of rows [0, nr) (Ws rows >= n are zero): each row's dot products
-// split over 256 / nr lanes (a shuffle tree joins them); the caller barriers
-__device__ __forceinline__ void gat_scores(const float* Ws, int Fs, const float* a_s, const float* a_d, int F,
-                                           const float* labels, int mode, int o, int n, int nr, float* ss, float* ts,
-                                           float* lab, const float* Ds = nullptr, float* rsum = nullptr) {
-  int sp = 1;   // lanes per row: a power of 2 (groups of aligned lanes)
-  while (sp < 16 && 2 * sp * nr <= kGatThreads) sp *= 2;
-  const int part = threadIdx.x & (sp - 1);
-  for (int r = threadIdx.x / sp; r < nr; r += kGatThreads / sp) {
-    // (fp64: the products of two floats are exact, so the scores are the
-    // rounded exact dot products whatever the lane split)
-    double s = 0.0, t = 0.0;
-    float sd = 0.f;
-    for (int f = part; f < F; f += sp) {
-      const double w = Ws[r * Fs + f];
-      s = fma(w, (double)a_s[f], s);
-      t = fma(w, (double)a_d[f], t);
-      if (Ds) sd += Ds[r * Fs + f];
-    }
-    for (int o2 = 1; o2 < sp; o2 <<= 1) {
-      s += __shfl_xor(s, o2);
-      t += __shfl_xor(t, o2);
-      sd += __shfl_xor(sd, o2);
-    }
-    if (part == 0) {
-      ss[r] = (float)s;
-      ts[r] = (float)t;
-      if (rsum) rsum[r] = sd;
-      lab[r] = (mode == 0 && r < n) ? labels[o + r] : 0.f;
-    }
-  }
-}
 
 // softmax attention + aggregation + bias + epilogue of one (segment, head)
 // from the LDS tile Ws (nr x Fs, zero rows past n) and its scores
@@ -182,57 +100,7 @@ __device__ __forceinline__ void gat_attend(const float* Ws, int Fs, const float*
       }
     }
     // epilogue per output row 16 rb + 4 q + v, feature 16 ct + r16
-    float lse[4] = {0.f, 0.f, 0.f, 0.f};
-    if (epi == 2) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        float zm = -INFINITY;
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct)
-          if (ct < nct && 16 * ct + r16 < F) zm = fmaxf(zm, elu(hv[ct][v]));
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) zm = fmaxf(zm, __shfl_xor(zm, o2));
-        float se = 0.f;
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct)
-          if (ct < nct && 16 * ct + r16 < F) se += expf(elu(hv[ct][v]) - zm);
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) se += __shfl_xor(se, o2);
-        lse[v] = zm + logf(se);
-      }
-    }
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) {
-      const int f = 16 * ct + r16;
-      if (ct < nct && f < F) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int io = 16 * rb + 4 * q + v;
-          if (io < n) {
-            const float h = hv[ct][v];
-            const float z = epi ? elu(h) : h;
-            if (epi) hp[(size_t)(o + io) * HF + c0 + f] = h;
-            y[(size_t)(o + io) * ldy + c0 + f] = epi == 2 ? z - lse[v] : z;
-          }
-        }
-      }
-    }
-  }
-}
-
-// rows past the last segment (zero-padded group buffers): zero outputs
-// (blk / nblk: this workgroup's index among the nblk serving the rows)
-__device__ __forceinline__ void gat_zero_pad_rows(int tot, int nrows, int HF, float* y, int ldy, float* hp,
-                                                  int blk = -1, int nblk = 0) {
-  if (blk < 0) {
-    blk = blockIdx.x;
-    nblk = gridDim.x;
-  }
-  for (size_t e = (size_t)tot * HF + (size_t)blk * kGatThreads + threadIdx.x; e < (size_t)nrows * HF;
-       e += (size_t)nblk * kGatThreads) {
-    const size_t r = e / HF, c = e - r * HF;
-    y[r * ldy + c] = 0.f;
-    if (hp) hp[e] = 0.f;
+    SGG_GAT_EPILOGUE_STORE(16 * rb)
   }
 }
 
@@ -733,6 +601,14 @@ __global__ void __launch_bounds__(256) gat_param_reduce_kernel(const float* __re
   }
 }
 
+// (rows: slab rows of heads partials each -- the segments of gat_bwd_kernel,
+// the column units of gat_wide.hip)
+void gat_param_reduce(const float* pda, const double* pdb, int rows, int heads, int F, float* da_src, float* da_dst,
+                      float* dbias, hipStream_t st) {
+  hipLaunchKernelGGL(gat_param_reduce_kernel, dim3(heads * 2 * F + (dbias ? F : 0)), dim3(256), 0, st, pda, pdb, rows,
+                     heads, F, da_src, da_dst, dbias);
+}
+
 static size_t gat_fwd_lds(int F, int max_seg) {
   const size_t nm = gat_r16(max_seg);
   return sizeof(float) * (nm * gat_fs(F) + 3 * nm + 2 * F) + 16;
@@ -849,8 +725,7 @@ extern "C" int sgg_gat_bwd_ex(const float* Wh, int heads, const float* a_src, co
                           epilogue, max_seg, hp, y, dy, lddy, dWh, nullptr, nullptr, pda, pdb, stream);
   if (rc) return rc;
   // (no segments: the reduce writes zero gradients)
-  hipLaunchKernelGGL(gat_param_reduce_kernel, dim3(heads * 2 * F + (dbias ? F : 0)), dim3(256), 0,
-                     (hipStream_t)stream, pda, pdb, nseg, heads, F, da_src, da_dst, dbias);
+  gat_param_reduce(pda, pdb, nseg, heads, F, da_src, da_dst, dbias, (hipStream_t)stream);
   SGG_RETURN_LAUNCH("sgg_gat_bwd_ex");
 }
 

@@ -170,6 +170,10 @@ SIGNATURES = {
     "sgg_gat_bwd_ex": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p,
                             _p]),
     "sgg_gat_bwd_ex_work_bytes": (_sz, [_i, _i, _i]),
+    "sgg_gat_wide_work_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "sgg_gat_fwd_wide": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "sgg_gat_bwd_wide": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p,
+                              _p, _p, _p, _p]),
     "sgg_gat_layer_lds_bytes": (_sz, [_i, _i, _i]),
     "sgg_gat_layer_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _p, _p,
                                _p, _p, _p, _i, _p]),

@@ -1591,6 +1591,60 @@ def pool_u_spec(pool):
 # ---------------------------------------------------------------------------
 # graph attention
 # ---------------------------------------------------------------------------
+def gat_wide_nodes(max_seg):
+    """gat_is_wide for a largest-segment size."""
+    from .scene import SGG_GAT_MAX_NODES, SGG_GAT_WIDE_MAX_NODES
+    if max_seg > SGG_GAT_WIDE_MAX_NODES:
+        raise ValueError("graph attention: a segment of %d nodes exceeds the bound of %d per segment "
+                         "(SGG_GAT_WIDE_MAX_NODES)" % (max_seg, SGG_GAT_WIDE_MAX_NODES))
+    return max_seg > SGG_GAT_MAX_NODES
+
+
+def gat_is_wide(graph):
+    """True when the graph's largest segment is above the LDS-resident
+    attention kernels' bound: every segment of the graph then goes through
+    sgg_gat_fwd_wide / sgg_gat_bwd_wide.  Raises (before any launch) above
+    their bound."""
+    return gat_wide_nodes(graph.max_seg)
+
+
+def _gat_fwd_wide(wh, heads, a_src, a_dst, lda, bias, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y):
+    """sgg_gat_fwd_wide; -> the work buffer (its forward part -- scores and
+    softmax row statistics -- is the backward's input, the rest its scratch)."""
+    lib = _lib()
+    n, HF = wh.shape
+    work = torch.empty(int(lib.sgg_gat_wide_work_floats(n, nseg, heads, F, max_seg)), device=wh.device,
+                       dtype=torch.float32)
+
+    def launch():
+        N.check(lib.sgg_gat_fwd_wide(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), lda, N.ptr(bias), N.ptr(labels),
+                                     N.ptr(seg_off), nseg, n, F, alpha, mode, epi, max_seg, N.ptr(hp), N.ptr(y), HF,
+                                     N.ptr(work), N.stream_ptr()), "sgg_gat_fwd_wide")
+    launch()
+    if timer.active and n > 0:
+        # scores 4 n HF, aggregation 2 n^2 F per head (n^2 bounded by n * max_seg); Wh in, y (+ hp) out
+        timer.add("sgg::gat_wide_scores_kernel+gat_fwd_wide_kernel", (n, HF, heads, max_seg),
+                  2.0 * n * max_seg * HF, 4.0 * n * HF * (3 if epi else 2), launch)
+    return work
+
+
+def _gat_bwd_wide(wh, heads, a_src, a_dst, lda, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y, dy, dWh,
+                  ds, dt, da_s, da_d, dbias, work):
+    lib = _lib()
+    n, HF = wh.shape
+
+    def launch():
+        N.check(lib.sgg_gat_bwd_wide(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), lda, N.ptr(labels), N.ptr(seg_off),
+                                     nseg, n, F, alpha, mode, epi, max_seg, N.ptr(hp), N.ptr(y), N.ptr(dy), HF,
+                                     N.ptr(dWh), N.ptr(ds), N.ptr(dt), N.ptr(da_s), N.ptr(da_d), N.ptr(dbias),
+                                     N.ptr(work), N.stream_ptr()), "sgg_gat_bwd_wide")
+    launch()
+    if timer.active and n > 0:
+        # _gat_bwd_ex_launch's model (the row units' second datt sweep not counted: algorithmic work)
+        timer.add("sgg::gat_bwd_wide_rows_kernel+gat_bwd_wide_cols_kernel", (n, HF, heads, max_seg),
+                  6.0 * n * max_seg * HF, 4.0 * n * HF * (4 if epi else 3), launch)
+
+
 class _GatAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wh, a, bias, labels, seg_off, nseg, max_seg, alpha, mode, epi, heads):
@@ -1606,17 +1660,22 @@ class _GatAttn(torch.autograd.Function):
         # complete-graph mode -- are written zero by the kernel)
         y = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         hp = torch.empty(n, HF, device=wh.device, dtype=torch.float32) if epi else None
-        N.check(lib.sgg_gat_fwd(N.ptr(wh), heads, N.ptr(a), N.ptr(bias), N.ptr(labels), N.ptr(seg_off), nseg, n, F,
-                                float(alpha), mode, epi, max_seg, N.ptr(hp), N.ptr(y), HF, N.stream_ptr()),
-                "sgg_gat_fwd")
+        work = None
+        if gat_wide_nodes(max_seg):
+            work = _gat_fwd_wide(wh, heads, a, a[F:], 2 * F, bias, labels, seg_off, nseg, F, float(alpha), mode, epi,
+                                 max_seg, hp, y)
+        else:
+            N.check(lib.sgg_gat_fwd(N.ptr(wh), heads, N.ptr(a), N.ptr(bias), N.ptr(labels), N.ptr(seg_off), nseg, n, F,
+                                    float(alpha), mode, epi, max_seg, N.ptr(hp), N.ptr(y), HF, N.stream_ptr()),
+                    "sgg_gat_fwd")
         ctx.meta = (labels, seg_off, nseg, max_seg, float(alpha), mode, epi, heads, bias is not None)
-        ctx.save_for_backward(wh, a, hp, y)
+        ctx.save_for_backward(wh, a, hp, y, work)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib()
-        wh, a, hp, y = ctx.saved_tensors
+        wh, a, hp, y, work = ctx.saved_tensors
         labels, seg_off, nseg, max_seg, alpha, mode, epi, heads, has_bias = ctx.meta
         n, HF = wh.shape
         F = HF // heads
@@ -1624,9 +1683,13 @@ class _GatAttn(torch.autograd.Function):
         dWh = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         ds = torch.empty(n, heads, device=wh.device, dtype=torch.float32)
         dt = torch.empty(n, heads, device=wh.device, dtype=torch.float32)
-        N.check(lib.sgg_gat_bwd(N.ptr(wh), heads, N.ptr(a), N.ptr(labels), N.ptr(seg_off), nseg, n, F, alpha, mode,
-                                epi, max_seg, N.ptr(hp), N.ptr(y), N.ptr(dy), HF, N.ptr(dWh), N.ptr(ds), N.ptr(dt),
-                                N.stream_ptr()), "sgg_gat_bwd")
+        if work is not None:
+            _gat_bwd_wide(wh, heads, a, a[F:], 2 * F, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y, dy,
+                          dWh, ds, dt, None, None, None, work)
+        else:
+            N.check(lib.sgg_gat_bwd(N.ptr(wh), heads, N.ptr(a), N.ptr(labels), N.ptr(seg_off), nseg, n, F, alpha, mode,
+                                    epi, max_seg, N.ptr(hp), N.ptr(y), N.ptr(dy), HF, N.ptr(dWh), N.ptr(ds), N.ptr(dt),
+                                    N.stream_ptr()), "sgg_gat_bwd")
         if not ctx.needs_input_grad[1] and not has_bias:
             return dWh, None, None, None, None, None, None, None, None, None, None
         dsdt = torch.cat([ds, dt], 1)                                       # n x [ds_h | dt_h]
@@ -1664,17 +1727,22 @@ class _GatAttnEx(torch.autograd.Function):
             bias = bias.contiguous()
         y = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         hp = torch.empty(n, HF, device=wh.device, dtype=torch.float32) if epi else None
-        N.check(lib.sgg_gat_fwd_ex(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), N.ptr(bias), N.ptr(labels),
-                                   N.ptr(seg_off), nseg, n, F, float(alpha), mode, epi, max_seg, N.ptr(hp), N.ptr(y),
-                                   HF, N.stream_ptr()), "sgg_gat_fwd_ex")
+        work = None
+        if gat_wide_nodes(max_seg):
+            work = _gat_fwd_wide(wh, heads, a_src, a_dst, F, bias, labels, seg_off, nseg, F, float(alpha), mode, epi,
+                                 max_seg, hp, y)
+        else:
+            N.check(lib.sgg_gat_fwd_ex(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), N.ptr(bias), N.ptr(labels),
+                                       N.ptr(seg_off), nseg, n, F, float(alpha), mode, epi, max_seg, N.ptr(hp),
+                                       N.ptr(y), HF, N.stream_ptr()), "sgg_gat_fwd_ex")
         ctx.meta = (labels, seg_off, nseg, max_seg, float(alpha), mode, epi, heads, bias is not None, F)
-        ctx.save_for_backward(wh, a_src, a_dst, hp, y)
+        ctx.save_for_backward(wh, a_src, a_dst, hp, y, work)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib()
-        wh, a_src, a_dst, hp, y = ctx.saved_tensors
+        wh, a_src, a_dst, hp, y, work = ctx.saved_tensors
         labels, seg_off, nseg, max_seg, alpha, mode, epi, heads, has_bias, F = ctx.meta
         n, HF = wh.shape
         dy = dy.contiguous()
@@ -1682,6 +1750,10 @@ class _GatAttnEx(torch.autograd.Function):
         da_s = torch.empty_like(a_src)
         da_d = torch.empty_like(a_dst)
         dbias = torch.empty(F, device=wh.device, dtype=torch.float32) if has_bias else None
+        if work is not None:
+            _gat_bwd_wide(wh, heads, a_src, a_dst, F, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y, dy,
+                          dWh, None, None, da_s, da_d, dbias, work)
+            return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None
         work = torch.empty(max(16, int(lib.sgg_gat_bwd_ex_work_bytes(nseg, heads, F))), device=wh.device,
                            dtype=torch.uint8)
         _gat_bwd_ex_launch(wh, heads, a_src, a_dst, labels, seg_off, nseg, n, F, alpha, mode, epi, max_seg, hp, y, dy,

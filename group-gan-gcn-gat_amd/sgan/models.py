@@ -297,8 +297,7 @@ class GATEncoder(nn.Module):
         if isinstance(h_states, (tuple, list)):
             h_states, x2 = h_states
         sc = _scenes(seq_start_end, h_states.device, scenes)
-        if sc.max_n > 128:
-            raise ValueError("GAT kernels hold <= 128 peds per scene (got %d)" % sc.max_n)
+        K.gat_wide_nodes(sc.max_n)   # a scene above the attention bound: ValueError before any launch
         nh = len(self.gat_intra.attentions)
         params = self.fused_params()
         need_grad = torch.is_grad_enabled() and (h_states.requires_grad or (x2 is not None and x2.requires_grad)
@@ -435,18 +434,17 @@ class BatchGATEncoder(nn.Module):
         """h_states: (B, n_units[0]) or its two column blocks (h, pool_h)."""
         dev = (h_states[0] if isinstance(h_states, tuple) else h_states).device
         sc = _scenes(seq_start_end, dev, scenes)
-        if sc.max_n > 128:
-            raise ValueError("GAT kernels hold <= 128 peds per scene (got %d)" % sc.max_n)
-        return self.gat_net(h_states, K.SegmentGraph(sc.scene_off, sc.S, sc.max_n, 1, None))
+        graph = K.SegmentGraph(sc.scene_off, sc.S, sc.max_n, 1, None)
+        K.gat_is_wide(graph)   # a scene above the attention bound: ValueError before any launch
+        return self.gat_net(h_states, graph)
 
     def forward_pair(self, ha, sca, hb, scb):
         """forward() of two batches (a without autograd) with each fused layer
         in one launch for both (BatchGAT.forward_pair)."""
-        for sc in (sca, scb):
-            if sc.max_n > 128:
-                raise ValueError("GAT kernels hold <= 128 peds per scene (got %d)" % sc.max_n)
-        return self.gat_net.forward_pair(ha, K.SegmentGraph(sca.scene_off, sca.S, sca.max_n, 1, None),
-                                         hb, K.SegmentGraph(scb.scene_off, scb.S, scb.max_n, 1, None))
+        ga = K.SegmentGraph(sca.scene_off, sca.S, sca.max_n, 1, None)
+        gb = K.SegmentGraph(scb.scene_off, scb.S, scb.max_n, 1, None)
+        K.gat_is_wide(ga), K.gat_is_wide(gb)   # a scene above the attention bound: ValueError before any launch
+        return self.gat_net.forward_pair(ha, ga, hb, gb)
 
 
 # ---------------------------------------------------------------------------

@@ -419,6 +419,8 @@ class _PaddedRepeat(SceneIndex):
 
 SGG_POOL_MAX_PEDS = 64          # include/sgg.h: scene bound of the LDS-resident pooling kernels
 SGG_POOL_WIDE_MAX_PEDS = 1024   # include/sgg.h: scene bound of the tiled (wide) pooling kernels
+SGG_GAT_MAX_NODES = 128         # include/sgg.h: segment bound of the LDS-resident attention kernels
+SGG_GAT_WIDE_MAX_NODES = 1024   # include/sgg.h: segment bound of the tiled (wide) attention kernels
 SGG_POOL_MAX_ROWS = 64   # chunk height bound of sgg_pool_fwd (a padded plan's LDS is sized for it)
 
 

@@ -44,6 +44,8 @@ const char* sgg_source_hash(void);
 #define SGG_POOL_WIDE_MAX_PEDS 1024  /* peds per scene of the tiled pooling kernels (= the group
                                       * index's bound)                                             */
 #define SGG_GAT_MAX_NODES 128  /* nodes per segment held LDS-resident by the attention kernel */
+#define SGG_GAT_WIDE_MAX_NODES 1024  /* nodes per segment of the tiled attention kernels
+                                      * (sgg_gat_*_wide; = the group index's bound)                */
 
 /* ------------------------------------------------------------------------
  * Dense node-feature transform on MFMA (v_mfma_f32_16x16x4_f32, exact fp32):
@@ -219,7 +221,9 @@ int sgg_pool_bwd_wide(const float* U, const float* pos, const float* A, const fl
  * (n x heads*F, pre-epilogue, bias included) is written when epilogue != 0
  * (needed by the backward).  Epilogue 2 requires heads == 1 and ldy == F.
  * Rows [seg_off[nseg], n) (zero-padded group buffers no segment covers)
- * get zero y / hp.  Segments larger than SGG_GAT_MAX_NODES are rejected.
+ * get zero y / hp.  max_seg above SGG_GAT_MAX_NODES is rejected here:
+ * sgg_gat_fwd_wide / sgg_gat_bwd_wide (below) take segments of up to
+ * SGG_GAT_WIDE_MAX_NODES nodes.
  */
 int sgg_gat_fwd(const float* Wh, int heads, const float* a, const float* bias, const float* labels,
                 const int32_t* seg_off, int nseg, int n, int F, float alpha, int mask_mode,
@@ -255,6 +259,35 @@ int sgg_gat_bwd_ex(const float* Wh, int heads, const float* a_src, const float* 
                    const int32_t* seg_off, int nseg, int n, int F, float alpha, int mask_mode, int epilogue,
                    int max_seg, const float* hp, const float* y, const float* dy, int lddy, float* dWh,
                    float* da_src, float* da_dst, float* dbias, void* work, void* stream);
+
+/* Graph attention for segments of up to SGG_GAT_WIDE_MAX_NODES nodes: the
+ * semantics of sgg_gat_fwd (mask modes, epilogues, heads side by side, bias,
+ * ldy, zero rows past the last segment; a segment larger than max_seg is
+ * clamped), with the pair space of a segment tiled instead of LDS-resident.
+ * On a segment that sgg_gat_fwd takes too, y and hp are bitwise its.
+ * a_src / a_dst: head h's vectors at a_src + h * lda, a_dst + h * lda (the
+ * `a` form: a, a + F, lda = 2F; the `_ex` form: lda = F).
+ * work: caller-owned, 16-byte aligned, sgg_gat_wide_work_floats(n, nseg,
+ * heads, F, max_seg) floats.  The forward writes its first 4 x r4(n x heads)
+ * floats (r4: rounded up to 4, at least 4) -- the scores s, t and the softmax
+ * row max and 1 / sum -- and the backward needs them unchanged; the rest is
+ * the backward's (dot, ds, the parameter-gradient partials). */
+size_t sgg_gat_wide_work_floats(int n, int nseg, int heads, int F, int max_seg);
+int sgg_gat_fwd_wide(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                     const float* bias, const float* labels, const int32_t* seg_off, int nseg, int n, int F,
+                     float alpha, int mask_mode, int epilogue, int max_seg, float* hp, float* y, int ldy,
+                     float* work, void* stream);
+/* Backward of sgg_gat_fwd_wide (two dependent launches, no floating-point
+ * atomics, every sum in a fixed order).  Always writes dWh (n x heads*F, zero
+ * past the last segment).  ds, dt (n x heads; both or neither): written as
+ * sgg_gat_bwd does, for a caller that finishes da itself.  da_src, da_dst
+ * (heads x F; both or neither) and dbias (F; only with them): finished on the
+ * device as sgg_gat_bwd_ex does, by one more fixed-order launch. */
+int sgg_gat_bwd_wide(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                     const float* labels, const int32_t* seg_off, int nseg, int n, int F, float alpha,
+                     int mask_mode, int epilogue, int max_seg, const float* hp, const float* y,
+                     const float* dy, int lddy, float* dWh, float* ds, float* dt, float* da_src,
+                     float* da_dst, float* dbias, float* work, void* stream);
 
 /* One layer of the sgangat family's batched GAT in one launch (GAT.py:71-86
  * text): InstanceNorm1d over each segment's rows (biased variance, eps; the

@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|...]"""
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|...]"""
 import os
 import sys
 
@@ -96,6 +96,48 @@ def poolwide(S, n, bn, reps=20):
         print("pool %-8s S=%3d n=%4d bn=%2d chunks=%5d rows=%2d gpw=%d  fwd %8.1f us %6.1f TF/s %5.3f ns/pair  "
               "bwd %8.1f us" % (name, S, n, bn, nchunks, max_rows, g, uf, flops / uf / 1e6, uf * 1e3 / (S * n * n), ub),
               flush=True)
+
+
+def gatwide(S, n, heads, F, reps=20):
+    """The tiled attention forward and backward (sgg_gat_fwd_wide /
+    sgg_gat_bwd_wide, parameter gradients finished) on S complete-graph
+    segments of n nodes; n <= 128: the resident kernels (sgg_gat_fwd_ex /
+    sgg_gat_bwd_ex) on the same operands next to them."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B, HF = S * n, heads * F
+    off = torch.arange(0, B + 1, n, dtype=torch.int32, device=dev)
+    wh = torch.randn(B, HF, device=dev)
+    a_s, a_d = torch.randn(heads, F, device=dev) * 0.5, torch.randn(heads, F, device=dev) * 0.5
+    bias = torch.randn(F, device=dev) * 0.1
+    dy = torch.randn(B, HF, device=dev)
+    y, hp, dWh = (torch.empty(B, HF, device=dev) for _ in range(3))
+    da_s, da_d, db = torch.empty_like(a_s), torch.empty_like(a_d), torch.empty_like(bias)
+    lib = N.load()
+    for name, wide in [("wide", True)] + ([("resident", False)] if n <= 128 else []):
+        if wide:
+            work = torch.empty(int(lib.sgg_gat_wide_work_floats(B, S, heads, F, n)), device=dev)
+            fwd = lambda: N.check(lib.sgg_gat_fwd_wide(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), F, N.ptr(bias), None,
+                                                       N.ptr(off), S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), HF,
+                                                       N.ptr(work), N.stream_ptr()), "fwd")
+            bwd = lambda: N.check(lib.sgg_gat_bwd_wide(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), F, None, N.ptr(off),
+                                                       S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), N.ptr(dy), HF,
+                                                       N.ptr(dWh), None, None, N.ptr(da_s), N.ptr(da_d), N.ptr(db),
+                                                       N.ptr(work), N.stream_ptr()), "bwd")
+        else:
+            work = torch.empty(int(lib.sgg_gat_bwd_ex_work_bytes(S, heads, F)), device=dev, dtype=torch.uint8)
+            fwd = lambda: N.check(lib.sgg_gat_fwd_ex(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), N.ptr(bias), None,
+                                                     N.ptr(off), S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), HF,
+                                                     N.stream_ptr()), "fwd")
+            bwd = lambda: N.check(lib.sgg_gat_bwd_ex(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), None, N.ptr(off), S, B,
+                                                     F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), N.ptr(dy), HF, N.ptr(dWh),
+                                                     N.ptr(da_s), N.ptr(da_d), N.ptr(db), N.ptr(work),
+                                                     N.stream_ptr()), "bwd")
+        uf = timeit(fwd, reps)
+        ub = timeit(bwd, reps)
+        pairs = float(S) * n * n * heads   # (i, j, head)
+        print("gat %-8s S=%3d n=%4d heads=%d F=%3d  fwd %8.1f us %6.3f ns/pair  bwd %8.1f us %6.3f ns/pair" % (
+            name, S, n, heads, F, uf, uf * 1e3 / pairs, ub, ub * 1e3 / pairs), flush=True)
 
 
 def lstm(B, T, H, decoder, reps=10, save=False):
@@ -228,6 +270,11 @@ if __name__ == "__main__":
             # (64 x 128: enough rows for chunks above gpw rows -- several passes per j-tile)
             for (S, n) in ((64, 64), (32, 128), (8, 256), (1, 1024), (64, 128)):
                 poolwide(S, n, bn)
+        sys.exit(0)
+    if what == "gatwide":   # the tiled attention kernels above 128 nodes, next to the resident ones at 128
+        for (S, n) in ((32, 128), (8, 256), (1, 1024)):
+            for (heads, F) in ((1, 72), (4, 16)):
+                gatwide(S, n, heads, F)
         sys.exit(0)
     if what == "lbwd":    # the discriminator encoder's backward with weight gradients
         for (B, T, H) in ((2560, 20, 48), (1280, 20, 48), (2560, 12, 32), (1280, 8, 32), (8192, 20, 48)):
