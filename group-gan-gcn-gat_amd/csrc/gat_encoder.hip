@@ -562,9 +562,10 @@ __device__ __forceinline__ float wmax(float v) {
 // 4], B[k = lane >> 4][j = lane & 15]; the D lane holds rows 4 (lane >> 4) + r,
 // column lane & 15.  Rows / columns past the edge read a clamped (valid)
 // element and are not stored; a reduction over rows masks them to zero.
-// k-steps per operand batch of lin / lin_t / wgrad (template NB): the forward
+// k-steps per operand batch of lin (its template parameter): the forward
 // kernel batches 4 (its 1024-thread workgroups leave it registers); the
-// backward sits at the 128-VGPR cap and keeps the plain loop (NB = 1)
+// backward sits at the 128-VGPR cap and keeps the plain loop (1), in lin as
+// in lin_t and wgrad
 __device__ __forceinline__ int mm_wave(int first) {
   const int nw = blockDim.x >> 6;
   return ((int)(threadIdx.x >> 6) + nw - first % nw) % nw;
@@ -626,7 +627,6 @@ __device__ __forceinline__ void lin(const float* in, int ldi, int rows, int K, c
 // out[r][k] (+)= sum_c d[r][c] W[k][c]   (input gradient of lin; N % 4 == 0;
 // out may be global memory)
 // (out2: columns >= ksplit go to out2 at pitch ldo2 instead)
-template <int kMmB = 1>
 __device__ __forceinline__ void lin_t(const float* d, int ldd, int rows, int N, const float* W, int ldw, int K, float* out, int ldo,
                       bool accum, int first = 0, float* out2 = nullptr, int ldo2 = 0, int ksplit = 0) {
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6, i = lane & 15, kq = lane >> 4;
@@ -636,21 +636,8 @@ __device__ __forceinline__ void lin_t(const float* d, int ldd, int rows, int N, 
     const float* pa = d + min(r0 + i, rows - 1) * ldd + kq;
     const float* pb = W + min(k0 + i, K - 1) * ldw + kq;
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (kMmB == 1) {
 #pragma unroll 2
-      for (int c = 0; c < N; c += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[c], pb[c], acc, 0, 0, 0);
-    } else
-    for (int c = 0; c < N; c += 4 * kMmB) {   // batched as in lin
-      float av[kMmB], bv[kMmB];
-#pragma unroll
-      for (int u = 0; u < kMmB; ++u) {
-        const int cc = min(c + 4 * u, N - 4);
-        av[u] = c + 4 * u < N ? pa[cc] : 0.f;
-        bv[u] = c + 4 * u < N ? pb[cc] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kMmB; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    }
+    for (int c = 0; c < N; c += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[c], pb[c], acc, 0, 0, 0);
     const int col = k0 + i;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -665,7 +652,6 @@ __device__ __forceinline__ void lin_t(const float* d, int ldd, int rows, int N, 
 
 // dst[k][c] = sum_r x[r][k] d[r][c]  (weight gradient of lin: to the slab,
 // ldo = N; or an LDS image)
-template <int kMmB = 1>
 __device__ __forceinline__ void wgrad(const float* x, int ldx, int rows, int K, const float* d, int ldd, int N, float* dst, int ldo,
                       int first = 0) {
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6, i = lane & 15, kq = lane >> 4;
@@ -675,26 +661,11 @@ __device__ __forceinline__ void wgrad(const float* x, int ldx, int rows, int K, 
     const float* pa = x + min(k0 + i, K - 1);
     const float* pb = d + min(c0 + i, N - 1);
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    // the lane's row r; a step covers rows r - kq .. r - kq + 3; batched as in lin
-    if constexpr (kMmB == 1) {
-      for (int r = kq; r < rows + kq; r += 4) {
-        const bool ok = r < rows;
-        const float av = ok ? pa[r * ldx] : 0.f, bv = ok ? pb[r * ldd] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-      }
-    } else
-    for (int r = kq; r < rows + kq; r += 4 * kMmB) {
-      float av[kMmB], bv[kMmB];
-#pragma unroll
-      for (int u = 0; u < kMmB; ++u) {
-        const int rr = r + 4 * u;
-        const bool ok = rr < rows;
-        av[u] = ok ? pa[rr * ldx] : 0.f;
-        bv[u] = ok ? pb[rr * ldd] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kMmB; ++u)
-        if (r + 4 * u < rows + kq) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+    // the lane's row r; a step covers rows r - kq .. r - kq + 3
+    for (int r = kq; r < rows + kq; r += 4) {
+      const bool ok = r < rows;
+      const float av = ok ? pa[r * ldx] : 0.f, bv = ok ? pb[r * ldd] : 0.f;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
     }
     const int col = c0 + i;
 #pragma unroll

@@ -178,13 +178,6 @@ __device__ long long g_lstm_prof[256];
 #define LUSE(x)
 #endif
 
-#ifndef SGG_MW_UPRE
-#define SGG_MW_UPRE 1   // the projection epilogue's Wu fragments fetched in the prologue (0: probe A/B only)
-#endif
-#ifndef SGG_MW_FWD_X3
-#define SGG_MW_FWD_X3 1   // the encoders' gate GEMM on split-bf16 MFMAs (0: the fp32 16x16x4 form; A/B builds)
-#endif
-
 namespace {
 
 // DEC / SAVE are compile-time, so the step loop carries no per-store
@@ -230,7 +223,7 @@ __device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk, const SggG
   // as accurate (tools/lstm_accuracy.py: 2.9e-7 vs 2.9e-7 from float64) but
   // rounds differently, and the generator's gradients downstream of the
   // pooling / GCN ReLUs are what the 64-ped error-ratio test pins)
-  constexpr bool X3 = !DEC && SGG_MW_FWD_X3 && H == 48;
+  constexpr bool X3 = !DEC && H == 48;
   __shared__ float hb[X3 ? 1 : 2][KS][64];        // fp32 form: h_{t-1}; X3: h_T for the epilogue
   __shared__ sgg_uint4v hx[X3 ? 2 : 1][3][2][64];  // X3: the pieces of h_{t-1} and the step input
   // X3 with saved states: h_t staged by (ped, unit) and written to h_all as
@@ -399,7 +392,7 @@ __device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk, const SggG
   // the projection epilogue's Wu fragments (see below), fetched now so their
   // latency hides under the recurrence: all of this wave's <= 8 tiles in
   // registers (NU <= 512, H <= 48, 16-byte aligned rows)
-  constexpr bool kUPre = SGG_MW_UPRE && !DEC && H <= 48;
+  constexpr bool kUPre = !DEC && H <= 48;
   constexpr int kUT = 8;
   const float* __restrict__ Wu = sg.Wu;
   const int ldwu = sg.ldwu, NU = sg.NU;
@@ -408,7 +401,7 @@ __device__ __forceinline__ void mw_fwd_body(const MwSeg& sg, int blk, const SggG
   // One tile per recurrence step (tile i at step i, the rest after the
   // loop): all eight at once in the prologue were ~100 loads per wave behind
   // the recurrence's operands (a wave tracks <= 63 outstanding), which held
-  // the first step back ~1.7 us (tools/lstm_mw_probe.hip, SGG_MW_UPRE A/B)
+  // the first step back ~1.7 us (tools/lstm_mw_probe.hip)
   float wu[kUPre ? kUT : 1][KS];
   float cuv[kUPre ? kUT : 1][4];
   auto load_wu = [&](int i) {   // (called with compile-time i only: wu stays in registers)
@@ -797,18 +790,6 @@ __global__ void __launch_bounds__(kMwThreads) lstm_mw_fwd3_kernel(MwSeg a, MwSeg
     mw_fwd_body<HC, false, SC>(c, blk - nblk_a - nblk_b);
 }
 
-#ifndef SGG_MW_BWD_DB
-#define SGG_MW_BWD_DB 1
-#endif
-#ifndef SGG_MW_BWD_X3
-#define SGG_MW_BWD_X3 1
-#endif
-// two operand sets for the owners of the encoder's weight-gradient form
-// without drel_in (kDB below; 0: one set, A/B builds)
-#ifndef SGG_MW_BWD_DB_NODX
-#define SGG_MW_BWD_DB_NODX 1
-#endif
-
 // NODX (encoder with weight gradients only): the input gradient drel_in is
 // not wanted -- the input is data, or comes from a no-grad rollout -- and
 // everything that forms it is left out at compile time: the helpers' A^T dG
@@ -848,7 +829,6 @@ __device__ __forceinline__ void mw_bwd_body(
   static_assert(!PDH || (!DEC && (H == 32 || H == 48)), "PDH: the encoders of the pooling nets (H = 32 / 48)");
   constexpr int MU = MwCfg<H>::MU, KS = MwCfg<H>::KS, G4 = MwCfg<H>::G4, HP = MwCfg<H>::HP;
   constexpr bool decoder = DEC, wgrad = WGRAD;
-  constexpr bool BX3 = SGG_MW_BWD_X3 != 0;   // dh_{t-1} partials on split-bf16 MFMAs (below)
   // with weight gradients the helper waves also take the db and dA sums
   // (hsum below), and for the encoder drel_in too, so the owners' step is the
   // recurrence alone (the decoder's owners keep drel_in: their dWp / dbp
@@ -1096,23 +1076,21 @@ __device__ __forceinline__ void mw_bwd_body(
   // the same W_hh^T entries as wt (their pieces, built once here; the
   // decoder's plain set for step 0 beside the folded one while MU <= 2).
   constexpr int KCH = (4 * MU + 7) / 8;
-  constexpr bool kWq0 = BX3 && DEC && MU <= 2;
-  bf16x8 wq[BX3 ? MU : 1][BX3 ? KCH : 1][3], wq0[kWq0 ? MU : 1][kWq0 ? KCH : 1][3];
-  auto build_wq = [&](const float (&w)[MU][MU][4], bf16x8 (&o)[BX3 ? MU : 1][BX3 ? KCH : 1][3]) {
-    if constexpr (BX3) {
+  constexpr bool kWq0 = DEC && MU <= 2;
+  bf16x8 wq[MU][KCH][3], wq0[kWq0 ? MU : 1][kWq0 ? KCH : 1][3];
+  auto build_wq = [&](const float (&w)[MU][MU][4], bf16x8 (&o)[MU][KCH][3]) {
 #pragma unroll
-      for (int mu = 0; mu < MU; ++mu)
+    for (int mu = 0; mu < MU; ++mu)
 #pragma unroll
-        for (int ch = 0; ch < KCH; ++ch) {
-          float v[8];
+      for (int ch = 0; ch < KCH; ++ch) {
+        float v[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int x = 8 * ch + j;
-            v[j] = x < 4 * MU ? w[mu][x >> 2][x & 3] : 0.f;
-          }
-          split8(v, o[mu][ch]);
+        for (int j = 0; j < 8; ++j) {
+          const int x = 8 * ch + j;
+          v[j] = x < 4 * MU ? w[mu][x >> 2][x & 3] : 0.f;
         }
-    }
+        split8(v, o[mu][ch]);
+      }
   };
   build_wq(wt, wq);
   if constexpr (kWq0) build_wq(wt0, wq0);
@@ -1158,7 +1136,7 @@ __device__ __forceinline__ void mw_bwd_body(
     float v[MU];
     __device__ float operator[](int i) const { return v[i]; }
   };
-  constexpr bool kDB = SGG_MW_BWD_DB && ((NODX && SGG_MW_BWD_DB_NODX != 0) || !(WGRAD && !DEC));
+  constexpr bool kDB = NODX || !(WGRAD && !DEC);
   typedef typename std::conditional<kDB, fvmu, FArr>::type CellV;
   struct StepIn {
     floatx4 a[MU];
@@ -1257,25 +1235,23 @@ __device__ __forceinline__ void mw_bwd_body(
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             wt[mu][i][r] = wt0_reg ? wt0[mu][i][r] : Whh[(r * H + slot_unit(g * MU + i, q)) * H + 16 * mu + c16];
-      if constexpr (BX3) {
-        if constexpr (kWq0) {
+      if constexpr (kWq0) {
 #pragma unroll
-          for (int mu = 0; mu < MU; ++mu)
+        for (int mu = 0; mu < MU; ++mu)
 #pragma unroll
-            for (int ch = 0; ch < KCH; ++ch)
+          for (int ch = 0; ch < KCH; ++ch)
 #pragma unroll
-              for (int pc3 = 0; pc3 < 3; ++pc3) wq[mu][ch][pc3] = wq0[mu][ch][pc3];
-        } else {
-          build_wq(wt, wq);
-        }
+            for (int pc3 = 0; pc3 < 3; ++pc3) wq[mu][ch][pc3] = wq0[mu][ch][pc3];
+      } else {
+        build_wq(wt, wq);
       }
     }
     floatx4 acc[MU];
 #pragma unroll
     for (int mu = 0; mu < MU; ++mu) acc[mu] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float vall[BX3 ? 8 * KCH : 1];   // X3: the lane's dG values in k order, zero padded
+    float vall[8 * KCH];   // X3: the lane's dG values in k order, zero padded
 #pragma unroll
-    for (int x = 0; x < (BX3 ? 8 * KCH : 1); ++x) vall[x] = 0.f;
+    for (int x = 0; x < 8 * KCH; ++x) vall[x] = 0.f;
 #pragma unroll
     for (int i = 0; i < MU; ++i) {
       const int j = g * MU + i;
@@ -1301,25 +1277,18 @@ __device__ __forceinline__ void mw_bwd_body(
       // adds nothing to the weight gradients
       const float vv[4] = {keep_if(dct * gg * ig * (1.f - ig), valid), keep_if(dct * ccp[i] * fg * (1.f - fg), valid),
                            keep_if(dct * ig * (1.f - gg * gg), valid), keep_if(d_o * og * (1.f - og), valid)};
-      if constexpr (BX3) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) vall[4 * i + r] = vv[r];
-        // a chunk's MFMAs as soon as its 8 values are in (slots 0-1, then 2-3)
-        if ((4 * i + 4) % 8 == 0 || i == MU - 1) {
-          const int ch = (4 * i) / 8;
-          float v8[8];
+      for (int r = 0; r < 4; ++r) vall[4 * i + r] = vv[r];
+      // a chunk's MFMAs as soon as its 8 values are in (slots 0-1, then 2-3)
+      if ((4 * i + 4) % 8 == 0 || i == MU - 1) {
+        const int ch = (4 * i) / 8;
+        float v8[8];
 #pragma unroll
-          for (int x = 0; x < 8; ++x) v8[x] = vall[8 * ch + x];
-          bf16x8 hp[3];
-          split8(v8, hp);
+        for (int x = 0; x < 8; ++x) v8[x] = vall[8 * ch + x];
+        bf16x8 hp[3];
+        split8(v8, hp);
 #pragma unroll
-          for (int mu = 0; mu < MU; ++mu) acc[mu] = mfma_x3(wq[mu][ch], hp, acc[mu]);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int mu = 0; mu < MU; ++mu) acc[mu] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[mu][i][r], vv[r], acc[mu], 0, 0, 0);
+        for (int mu = 0; mu < MU; ++mu) acc[mu] = mfma_x3(wq[mu][ch], hp, acc[mu]);
       }
       if (wgrad) {
 #pragma unroll
@@ -1445,28 +1414,28 @@ __device__ __forceinline__ void mw_bwd_body(
   LMARK(62);
 }
 
-#define SGG_MW_BWD_PARAMS                                                                                         \
+#define SGG_MWB_PARAMS                                                                                            \
   const float *__restrict__ A, const float *__restrict__ Whh, const float *__restrict__ Wp,                      \
       const float *__restrict__ h_all, const float *__restrict__ c_tile, const float *__restrict__ act_tile,     \
       const float *__restrict__ rel, const float *__restrict__ rel_out, const float *__restrict__ dh_last,       \
       const float *__restrict__ dout, int T, int B, float *__restrict__ dh0, float *__restrict__ drel_in,        \
       float *__restrict__ drel_tot, float *__restrict__ wpart, const float *__restrict__ dout2, int bsplit,      \
       int t_stop, int t_sh, int Bsrc
-#define SGG_MW_BWD_ARGS                                                                                           \
+#define SGG_MWB_ARGS                                                                                              \
   A, Whh, Wp, h_all, c_tile, act_tile, rel, rel_out, dh_last, dout, T, B, dh0, drel_in, drel_tot, wpart, dout2,  \
       bsplit, t_stop, t_sh, Bsrc
 
 template <int H, bool DEC, bool WGRAD>
-__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_kernel(SGG_MW_BWD_PARAMS) {
-  mw_bwd_body<H, DEC, WGRAD, false>(SGG_MW_BWD_ARGS);
+__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_kernel(SGG_MWB_PARAMS) {
+  mw_bwd_body<H, DEC, WGRAD, false>(SGG_MWB_ARGS);
 }
 
 // the encoder's weight-gradient form without input gradients (drel_in NULL;
 // mw_bwd_body NODX).  Built for the hidden sizes of the reference's encoders
 // (mw_bwd_nodx_built); elsewhere a NULL drel_in stays an argument error.
 template <int H>
-__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_kernel(SGG_MW_BWD_PARAMS) {
-  mw_bwd_body<H, false, true, true>(SGG_MW_BWD_ARGS);
+__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_kernel(SGG_MWB_PARAMS) {
+  mw_bwd_body<H, false, true, true>(SGG_MWB_ARGS);
 }
 constexpr bool mw_bwd_nodx_built(int H) { return H == 16 || H == 32 || H == 48; }
 
@@ -1474,13 +1443,13 @@ constexpr bool mw_bwd_nodx_built(int H) { return H == 16 || H == 32 || H == 48; 
 // drel_in (WGRAD: eight waves + riders; else the four-wave input-gradient
 // form, sgg_lstm_bwd_tail's too), and the weight-gradient form without it
 template <int H, bool WGRAD>
-__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_pdh_kernel(SGG_MW_BWD_PARAMS,
+__global__ void __launch_bounds__(WGRAD ? 2 * kMwThreads : kMwThreads) lstm_mw_bwd_pdh_kernel(SGG_MWB_PARAMS,
                                                                                               MwPoolDh pd) {
-  mw_bwd_body<H, false, WGRAD, false, true>(SGG_MW_BWD_ARGS, &pd);
+  mw_bwd_body<H, false, WGRAD, false, true>(SGG_MWB_ARGS, &pd);
 }
 template <int H>
-__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_pdh_kernel(SGG_MW_BWD_PARAMS, MwPoolDh pd) {
-  mw_bwd_body<H, false, true, true, true>(SGG_MW_BWD_ARGS, &pd);
+__global__ void __launch_bounds__(2 * kMwThreads) lstm_mw_bwd_nodx_pdh_kernel(SGG_MWB_PARAMS, MwPoolDh pd) {
+  mw_bwd_body<H, false, true, true, true>(SGG_MWB_ARGS, &pd);
 }
 constexpr bool mw_bwd_pdh_built(int H) { return H == 32 || H == 48; }
 

@@ -25,11 +25,6 @@ DUAL_POOL_BWD = os.environ.get("SGG_DUAL_POOL_BWD", "1") != "0"
 # backward that consumes it, the h^T dU partials riding in that launch
 # (sgg_lstm_bwd_pooldh; PoolDhSlot); "0": the launches above
 POOL_DH_IN_LSTM = os.environ.get("SGG_POOL_DH_IN_LSTM", "1") != "0"
-# weight-gradient reductions of the backward on a side stream (needed only by
-# the optimizer step, which joins it).  Off by default: measured slower at
-# configs[1] (61.1k vs 68.9k scenes/s graph-replayed, 12.4k vs 14.8k eager
-# real data) -- the cross-stream edges cost more than the overlap wins
-SIDE_STREAM = os.environ.get("SGG_SIDE_STREAM", "0") == "1"
 
 
 # SGG_DEBUG=1: host-side consistency checks that cost a device read
@@ -109,8 +104,8 @@ def private_stream(tag, device=None):
     outside torch's stream pool (32 pooled streams handed out round-robin),
     so it can never be the stream of a torch.distributed process group or of
     other torch code: the graph captures (GraphedTrainer, tag "capture"), the
-    weight-gradient side stream ("side"), the overlap plan's second stream
-    ("overlap") and the launch timer ("timer") run on such streams."""
+    overlap plan's second stream ("overlap") and the launch timer ("timer")
+    run on such streams."""
     global _hiprt
     import ctypes
     dev = torch.cuda.current_device() if device is None else torch.device(device).index
@@ -131,49 +126,6 @@ def private_stream(tag, device=None):
             raise N.NativeError("hipStreamCreateWithFlags failed (%d)" % rc)
         st = _private[key] = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", dev))
     return st
-
-
-class _Side:
-    stream = None
-    origin = None   # the stream that must wait for the side work
-    keep = []
-    active = False
-
-
-@contextlib.contextmanager
-def side(*keep):
-    """Run the block's launches on the weight-gradient side stream: it first
-    waits for everything issued so far on the current stream; the tensors in
-    `keep` (read by the block, allocated on the current stream) stay alive
-    until side_join().  Off (SGG_SIDE_STREAM=0): the block runs in line."""
-    if not SIDE_STREAM:
-        yield
-        return
-    cur = torch.cuda.current_stream()
-    if _Side.stream is None or _Side.stream.device != cur.device:
-        _Side.stream = private_stream("side", cur.device)
-    st = _Side.stream
-    st.wait_stream(cur)
-    _Side.keep.extend(t for t in keep if t is not None)
-    if not _Side.active:
-        _Side.active = True
-        _Side.origin = cur
-        try:   # inside a backward pass: join when it ends (any optimizer, e.g. torch.optim.Adam, then sees .grad)
-            torch.autograd.Variable._execution_engine.queue_callback(side_join)
-        except RuntimeError:
-            pass    # outside backward: the caller joins
-    with torch.cuda.stream(st):
-        yield
-
-
-def side_join():
-    """The stream the side work was forked from waits for it (end of the
-    backward pass, or explicitly before reading .grad); no-op when idle."""
-    if _Side.active:
-        _Side.origin.wait_stream(_Side.stream)
-        _Side.keep.clear()
-        _Side.active = False
-        _Side.origin = None
 
 
 def xw_raw(x, w, bias=None, trans_w=False, act=0, out=None, mask=None, prec=None):
@@ -606,8 +558,7 @@ class _XW(torch.autograd.Function):
             dx = xw_raw(dy, w, None, not ctx.trans_w, 0, mask=m, prec="fp32")
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             # X^T dY (K x N); nn.Linear-layout weights take it transposed (N x K)
-            with side(x, dy, m):
-                dw, cs = xtw(x, dy, colsum=True, trans_c=ctx.trans_w, mask=m)
+            dw, cs = xtw(x, dy, colsum=True, trans_c=ctx.trans_w, mask=m)
             db = cs if ctx.has_bias else None
         return dx, dw, db, None, None
 
@@ -1388,7 +1339,7 @@ class _Pool(torch.autograd.Function):
             timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
         dh = None
         H = h.shape[1]
-        dual = need[0] and wgrad and DUAL_POOL_BWD and not SIDE_STREAM and H <= 64
+        dual = need[0] and wgrad and DUAL_POOL_BWD and H <= 64
         # armed (social_pool): neither product is launched here -- the encoder's backward forms dh in its
         # prologue and carries the h^T dU partials (sgg_lstm_bwd_pooldh); what is returned as the gradient of
         # h is only the buffer by which that backward recognises its source
@@ -1429,24 +1380,23 @@ class _Pool(torch.autograd.Function):
                 dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
         if not wgrad:
             return dh, None, None, None, None, None, None, None, None, None, None, None
-        with side(part, h, dU, W1, We, be):
-            # one launch after the dW1h partials: dW2, db2 (slab [dW2 | dA | db2]
-            # row sums), dW1h = dU^T h, dc = sum_j dU_j, and the fold backward
-            # of (dA, dc) -> dW1e, dWe, dbe
-            rows = part.shape[0]
-            if (not dual and not hand) or (hand and ws is None):
-                ws, splits = xtw_partial(h, dU, colsum=True)
-            dW1 = torch.empty_like(W1)
-            dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
-            db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
-            dc = torch.empty(512, device=h.device, dtype=torch.float32)
-            gf = GradFinish()
-            gf.rowsum(part, rows, P, 0, bn * 512, dW2)
-            gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
-            gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
-            _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
-                                  dW=dW1[:, :E])
-            gf.run()   # (with riding partials: queued, issued after the encoder's backward has written them)
+        # one launch after the dW1h partials: dW2, db2 (slab [dW2 | dA | db2]
+        # row sums), dW1h = dU^T h, dc = sum_j dU_j, and the fold backward
+        # of (dA, dc) -> dW1e, dWe, dbe
+        rows = part.shape[0]
+        if (not dual and not hand) or (hand and ws is None):
+            ws, splits = xtw_partial(h, dU, colsum=True)
+        dW1 = torch.empty_like(W1)
+        dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
+        db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
+        dc = torch.empty(512, device=h.device, dtype=torch.float32)
+        gf = GradFinish()
+        gf.rowsum(part, rows, P, 0, bn * 512, dW2)
+        gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
+        gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
+        _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
+                              dW=dW1[:, :E])
+        gf.run()   # (with riding partials: queued, issued after the encoder's backward has written them)
         return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None, None
 
 
@@ -1568,10 +1518,9 @@ def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, dh_in
     ONLY gradient reaching the encoder's h_T through autograd; the backward
     then hands dU to the encoder's backward (PoolDhSlot) where the kernels
     take it and it pays (sgg_lstm_bwd_pooldh_pays): U from that encoder's
-    epilogue, no wide scene, H = 32 / 48, the peds' workgroups in one round,
-    no side stream."""
+    epilogue, no wide scene, H = 32 / 48, the peds' workgroups in one round."""
     slot = None
-    if dh_in_lstm and POOL_DH_IN_LSTM and not SIDE_STREAM and U is not None and torch.is_grad_enabled():
+    if dh_in_lstm and POOL_DH_IN_LSTM and U is not None and torch.is_grad_enabled():
         slot = getattr(U, "_sgg_pdh", None)
         if slot is not None and (pool_is_wide(scenes)
                                  or not _lib().sgg_lstm_bwd_pooldh_pays(h.numel() // h.shape[-1], h.shape[-1])):
@@ -1880,8 +1829,7 @@ class _GatLayer(torch.autograd.Function):
         dxn = xw_raw(dWh, w_all, None, True, 0, prec="fp32")
         dw = None
         if ctx.needs_input_grad[2]:
-            with side(xn, dWh):
-                dw_all = xtw(xn, dWh)
+            dw_all = xtw(xn, dWh)
             dw = dw_all.view(K, H, F).permute(1, 0, 2)
         dx = torch.empty(n, K, device=dev, dtype=torch.float32)
         N.check(lib.sgg_seg_norm_bwd(N.ptr(xn), K, N.ptr(dxn), K, K, N.ptr(seg_off), nseg, N.ptr(rstd), N.ptr(dx), K,
@@ -3006,8 +2954,7 @@ class _LstmEncoder(torch.autograd.Function):
                       (T, B, 0, int(wgrad)), fl, nb, launch)
         grads = (None,) * 6
         if wgrad:
-            with side(wpart, h_all, rel, W_ih, We, be):
-                grads = _lstm_finish(wpart, H, W_ih, We, be)
+            grads = _lstm_finish(wpart, H, W_ih, We, be)
         return (drel_in,) + grads + (dh0, None, None, None, None, None)   # (drel_in None: not wanted, not computed)
 
 
@@ -3155,15 +3102,14 @@ class _LstmDecoder(torch.autograd.Function):
             timer.add(lib.sgg_lstm_kernel_name(H, B, 1, int(wgrad), 1).decode(), (T, B, 1, int(wgrad)), fl, nb, launch)
         grads = (None,) * 6
         dWp = dbp = None
-        with side(wpart, h_all, rel, rel_out, drel_tot, W_ih, We, be):
-            if wgrad:
-                if need_p:   # accumulated by the kernel into the slab rows' last columns
-                    dWp = torch.empty(2, H, device=dev, dtype=torch.float32)
-                    dbp = torch.empty(2, device=dev, dtype=torch.float32)
-                P = wpart.shape[1] - 2 * H - 2
-                grads = _lstm_finish(wpart, H, W_ih, We, be, ((P, 2 * H, dWp), (P + 2 * H, 2, dbp)) if need_p else ())
-            elif need_p:   # a frozen LSTM under a trainable hidden2pos
-                dWp, dbp = xtw(h_all[1:].reshape(T * B, H), drel_tot.view(T * B, 2), colsum=True, trans_c=True)
+        if wgrad:
+            if need_p:   # accumulated by the kernel into the slab rows' last columns
+                dWp = torch.empty(2, H, device=dev, dtype=torch.float32)
+                dbp = torch.empty(2, device=dev, dtype=torch.float32)
+            P = wpart.shape[1] - 2 * H - 2
+            grads = _lstm_finish(wpart, H, W_ih, We, be, ((P, 2 * H, dWp), (P + 2 * H, 2, dbp)) if need_p else ())
+        elif need_p:   # a frozen LSTM under a trainable hidden2pos
+            dWp, dbp = xtw(h_all[1:].reshape(T * B, H), drel_tot.view(T * B, 2), colsum=True, trans_c=True)
         return (drel_in[0],) + grads + (dh0, None, dWp, dbp, None, None, None)
 
 

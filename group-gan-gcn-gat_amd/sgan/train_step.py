@@ -267,7 +267,6 @@ class GanTrainer:
 
     def _finish(self, params, opt, loss_terms, clip):
         """all-reduce grads (+ loss values), clip, step."""
-        K.side_join()   # the weight gradients of the side stream (normally joined at the end of backward)
         K.pooldh_check()   # (a pooling backward's dU that no encoder backward took: raises)
         K.grad_flush()  # the backward ops' queued weight-gradient finishes (KernelOps.defer_finish)
         grads = [p.grad for p in params if p.grad is not None]

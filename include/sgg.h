@@ -90,7 +90,7 @@ int sgg_xw_bf16(const float* X, int ldx, const float* Xmask, int ldm, const floa
  * sgg_pool_plan from the host copy of scene_off and copied to the device by
  * the caller (once per batch).  sgg_pool_plan returns the number of chunks
  * (<= cap) or SGG_E_ARG, the largest chunk height in *max_rows and the
- * 16-pair groups per wave in *gpw (1, 2, 4 or 8: the widest that still gives
+ * 16-pair groups per wave in *gpw (1, 2 or 4: the widest that still gives
  * >= target_chunks workgroups, capped by max_gpw when > 0; ~2-4x the CU
  * count keeps small batches busy).
  * Pass max_rows and gpw unchanged to sgg_pool_fwd.  A chunk with i1 <= i0 is

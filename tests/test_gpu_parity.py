@@ -418,14 +418,13 @@ def test_fused_lstm_other_families(H, T, decoder, B):
     test_fused_lstm_vs_oracle(H, T, decoder, B)
 
 
-@pytest.mark.parametrize("form", ["SGG_POOL_RESIDENT", "SGG_POOL_V"])
 @pytest.mark.parametrize("bn", [8, 48])
-def test_pool_resident_equals_tiled(bn, form, monkeypatch):
-    """sgg_pool_fwd's alternative fp32 forms -- resident (W2^T and the scene's
-    U rows in LDS, used when they fit) and fragment-native k-tiles -- against
-    the k-tiled form on the same chunk table: the same MFMA sequence, so
-    outputs and argmax are bitwise equal.  (The split-bf16 form, the default
-    for bn 32 / 48, is off here: test_pool_x3_vs_fp32.)"""
+def test_pool_v_equals_tiled(bn, monkeypatch):
+    """sgg_pool_fwd's fragment-native k-tiles (pool_fwd_v_kernel, the default
+    on small grids; SGG_POOL_V=0 turns it off) against the k-tiled form on
+    the same chunk table: the same MFMA sequence, so outputs and argmax are
+    bitwise equal.  (The split-bf16 form, the default for bn 32 / 48, is off
+    here: test_pool_x3_vs_fp32.)"""
     from sgan import _native as N
     from sgan import kernels as K
     from sgan.scene import SceneIndex
@@ -443,10 +442,7 @@ def test_pool_resident_equals_tiled(bn, form, monkeypatch):
     chunks, nchunks, max_rows, gpw = sc.pool_plan(bn)
     res = []
     for tiled in (False, True):
-        if tiled:
-            monkeypatch.delenv(form)
-        else:
-            monkeypatch.setenv(form, "1")
+        monkeypatch.setenv("SGG_POOL_V", "0" if tiled else "1")
         out = torch.empty(B, bn, device=DEV)
         am = torch.empty(B, bn, device=DEV, dtype=torch.int32)
         N.check(lib.sgg_pool_fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(sc.scene_off),
@@ -461,7 +457,7 @@ def test_pool_resident_equals_tiled(bn, form, monkeypatch):
         r = pc[s0:s1].unsqueeze(0) - pc[s0:s1].unsqueeze(1)          # [i, j] = p_j - p_i
         hid = torch.relu(Uc[s0:s1].unsqueeze(0) + r @ Ac.t())          # (i, j, 512)
         ref[s0:s1] = torch.relu(hid @ Wc.t() + bc).max(1)[0]
-    close(res[0][0], ref.numpy(), rtol=1e-5, what="pool resident")
+    close(res[0][0], ref.numpy(), rtol=1e-5, what="pool k-tiles")
 
 
 @pytest.mark.parametrize("bn", [32, 48])
