@@ -17,6 +17,7 @@
 // y, so the concatenation of heads (GAT.py:86) is free.  `bias` (F, shared by
 // the heads, GAT.py:41) is added to the aggregate before the epilogue.
 #include "gat_common.h"
+#include "dropout_common.h"
 
 namespace sgg {
 
@@ -42,12 +43,14 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // att @ Wh reads only Wh (LDS) -- no attention matrix is stored.
 
 // softmax attention + aggregation + bias + epilogue of one (segment, head)
-// from the LDS tile Ws (nr x Fs, zero rows past n) and its scores
-template <int NM>
+// from the LDS tile Ws (nr x Fs, zero rows past n) and its scores.  DROP:
+// attention dropout (dk: the (site, head)'s mask key, dropout_common.h) on the
+// normalised attention -- row o + i of the node array, in-segment column j
+template <int NM, bool DROP = false>
 __device__ __forceinline__ void gat_attend(const float* Ws, int Fs, const float* ss, const float* ts,
                                            const float* lab, int o, int n, int nr, int F, int HF, int c0, float alpha,
                                            int mode, int epi, const float* __restrict__ bias, float* __restrict__ hp,
-                                           float* __restrict__ y, int ldy) {
+                                           float* __restrict__ y, int ldy, const DropKey dk = DropKey{}) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, q = lane >> 4;
   const int nct = (F + 15) >> 4;
@@ -84,6 +87,11 @@ __device__ __forceinline__ void gat_attend(const float* Ws, int Fs, const float*
     const float inv = iv ? 1.f / sum : 0.f;
 #pragma unroll
     for (int m = 0; m < NM; ++m) p[m] *= inv;
+    if constexpr (DROP) {
+#pragma unroll
+      for (int m = 0; m < NM; ++m)
+        if (m < nm) p[m] = drop_word(dk, (uint32_t)(o + i), (uint32_t)(4 * m + q)) >= dk.thr ? p[m] * dk.scale : 0.f;
+    }
     // out = att @ Wh (+ bias), 16-feature column tiles
     floatx4 hv[8];
 #pragma unroll
@@ -104,42 +112,16 @@ __device__ __forceinline__ void gat_attend(const float* Ws, int Fs, const float*
   }
 }
 
-template <int NM>   // 4-node k-steps held per lane: segments of <= 4 NM nodes
-__global__ void __launch_bounds__(kGatThreads) gat_fwd_kernel(
-    const float* __restrict__ Wh, int heads, const float* __restrict__ a_src, const float* __restrict__ a_dst, int lda,
-    const float* __restrict__ bias, const float* __restrict__ labels, const int32_t* __restrict__ seg_off, int nseg,
-    int nrows, int F, float alpha, int mode, int epi, int max_seg, float* __restrict__ hp, float* __restrict__ y,
-    int ldy) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int Fs = gat_fs(F), F4 = (F + 3) & ~3;
-  const int nmax = gat_r16(max_seg);
-  const int HF = heads * F;
-  gat_zero_pad_rows(seg_off[nseg], nrows, HF, y, ldy, epi ? hp : nullptr);
-  float* Ws = reinterpret_cast<float*>(smem);   // nmax x Fs
-  float* ss = Ws + nmax * Fs;                   // nmax
-  float* ts = ss + nmax;                        // nmax
-  float* lab = ts + nmax;                       // nmax
-  float* al = lab + nmax;                       // 2F: the head's a_src | a_dst
-  for (int gh = blockIdx.x; gh < nseg * heads; gh += gridDim.x) {
-    const int g = gh / heads, hd = gh - g * heads;
-    const int o = seg_off[g];
-    // (a segment larger than the caller's max_seg would overrun the LDS plan:
-    // clamped, memory-safe; the host builds max_seg from the same offsets)
-    const int n = min(seg_off[g + 1] - o, nmax);
-    if (n <= 0) continue;
-    const int c0 = hd * F;
-    const int nr = gat_r16(n);
-    stage_block(nr, F4, n, F, [&](int r, int f) { return Wh[(size_t)(o + r) * HF + c0 + f]; },
-                [&](int r, int f, float v) { Ws[r * Fs + f] = v; });
-    for (int f = threadIdx.x; f < 2 * F; f += kGatThreads)
-      al[f] = f < F ? a_src[(size_t)lda * hd + f] : a_dst[(size_t)lda * hd + f - F];
-    __syncthreads();
-    gat_scores(Ws, Fs, al, al + F, F, labels, mode, o, n, nr, ss, ts, lab);
-    __syncthreads();
-    gat_attend<NM>(Ws, Fs, ss, ts, lab, o, n, nr, F, HF, c0, alpha, mode, epi, bias, hp, y, ldy);
-    __syncthreads();  // LDS reused by the next segment
-  }
-}
+// gat_fwd_kernel<NM> / gat_bwd_kernel<NJT> and their forms with attention
+// dropout, gat_fwd_drop_kernel<NM> / gat_bwd_drop_kernel<NJT>: one text
+// (gat_kernels.h) compiled twice -- with the body as a shared device function
+// the kernels without dropout compile to other instruction streams
+#define SGG_GAT_DROP 0
+#include "gat_kernels.h"
+#undef SGG_GAT_DROP
+#define SGG_GAT_DROP 1
+#include "gat_kernels.h"
+#undef SGG_GAT_DROP
 
 // One batched-GAT layer of the sgangat family in one launch (GAT.py:71-86
 // text: InstanceNorm1d over the scene's nodes, then the multi-head attention
@@ -331,241 +313,6 @@ static size_t gat_layer_lds(int K, int F, int max_seg) {
          sizeof(float) * (nm * (Kp + 1) + Kp * (((F + 15) & ~15) + 1) + nm * gat_fs(F) + 3 * nm + 3 * F) + 16;
 }
 
-// Backward.  Per row block (in the C layout: lane = column j, rows 4 (lane >>
-// 4) + v): the attention recomputed, datt = dhp @ Wh^T on MFMA, the softmax
-// and LeakyReLU backward to dz, its row sums (ds) and per-block column sums
-// (dt, summed over the blocks in order afterwards); the attention goes to LDS
-// for dWh = att^T @ dhp (MFMA over the rows) + ds a_src + dt a_dst.
-// With the slabs (sgg_gat_bwd_ex) each (segment, head) also writes its
-// partials of the parameter gradients: da_src = Wh^T ds, da_dst = Wh^T dt
-// (pda, 2F floats) and the bias gradient's column sums of dhp (pdb, F doubles:
-// a near-cancelling sum, the next layer's instance norm removes each
-// feature's scene mean); gat_param_reduce_kernel sums them in a fixed order.
-template <int NJT>  // 16-node column tiles: segments of <= 16 NJT nodes
-__global__ void __launch_bounds__(kGatThreads) gat_bwd_kernel(
-    const float* __restrict__ Wh, int heads, const float* __restrict__ a_src, const float* __restrict__ a_dst, int lda,
-    const float* __restrict__ labels, const int32_t* __restrict__ seg_off, int nseg, int nrows, int F, float alpha,
-    int mode, int epi, int max_seg, const float* __restrict__ hp, const float* __restrict__ y,
-    const float* __restrict__ dy, int lddy, float* __restrict__ dWh, float* __restrict__ ds_out,
-    float* __restrict__ dt_out, float* __restrict__ pda, double* __restrict__ pdb) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int gfirst = min((int)blockIdx.x / heads, nseg);
-  const int tot = seg_off[nseg], ofirst = seg_off[gfirst], efirst = seg_off[min(gfirst + 1, nseg)];
-  {  // rows past the last segment: zero gradients
-    const size_t r0 = tot, w = (size_t)heads * (F + 2);
-    for (size_t e = r0 * w + blockIdx.x * kGatThreads + threadIdx.x; e < (size_t)nrows * w;
-         e += (size_t)gridDim.x * kGatThreads) {
-      const size_t r = e / w, c = e - r * w;
-      if (c < (size_t)heads * F) dWh[r * heads * F + c] = 0.f;
-      else if (!ds_out) continue;
-      else if (c < (size_t)heads * (F + 1)) ds_out[r * heads + c - (size_t)heads * F] = 0.f;
-      else dt_out[r * heads + c - (size_t)heads * (F + 1)] = 0.f;
-    }
-  }
-  const int Fs = gat_fs(F), F4 = (F + 3) & ~3;
-  const int nmax = gat_r16(max_seg), Na = nmax + 4;
-  float* Ws = reinterpret_cast<float*>(smem);  // nmax x Fs
-  float* Ds = Ws + nmax * Fs;                  // nmax x Fs  (d hp)
-  float* At = Ds + nmax * Fs;                  // nmax x Na  (att)
-  float* ss = At + nmax * Na;
-  float* ts = ss + nmax;
-  float* lab = ts + nmax;
-  float* dss = lab + nmax;
-  float* dts = dss + nmax;
-  float* rsum = dts + nmax;                    // epilogue 2: row sums of dy
-  float* dtp = rsum + nmax;                    // (nmax / 16) x nmax column partials of dz
-  float* al = dtp + (nmax / 16) * nmax;        // 2F: the head's a_src | a_dst
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r16 = lane & 15, q = lane >> 4;
-  const int HF = heads * F;
-  const int nct = (F + 15) >> 4;
-  for (int gh = blockIdx.x; gh < nseg * heads; gh += gridDim.x) {
-    const int g = gh / heads, hd = gh - g * heads;
-    const int o = gh == (int)blockIdx.x ? ofirst : seg_off[g];
-    const int n = min((gh == (int)blockIdx.x ? efirst : seg_off[g + 1]) - o, nmax);   // (LDS plan bound)
-    if (n <= 0) {
-      for (int c = threadIdx.x; c < 3 * F; c += kGatThreads) {
-        if (c < 2 * F) {
-          if (pda) pda[(size_t)gh * 2 * F + c] = 0.f;
-        } else if (pdb) {
-          pdb[(size_t)gh * F + c - 2 * F] = 0.0;
-        }
-      }
-      continue;
-    }
-    const float* as = al;
-    const float* ad = al + F;
-    const int c0 = hd * F;
-    const int nr = gat_r16(n), nrb = nr >> 4;
-    for (int f = threadIdx.x; f < 2 * F; f += kGatThreads)
-      al[f] = f < F ? a_src[(size_t)lda * hd + f] : a_dst[(size_t)lda * hd + f - F];
-    stage_block(nr, F4, n, F, [&](int r, int f) { return Wh[(size_t)(o + r) * HF + c0 + f]; },
-                [&](int r, int f, float v) { Ws[r * Fs + f] = v; });
-    stage_block(
-        nr, F4, n, F,
-        [&](int r, int f) {
-          const size_t row = (size_t)(o + r);
-          const float d = dy[row * lddy + c0 + f];
-          return epi == 1 ? d * elu_grad(hp[row * HF + c0 + f]) : d;
-        },
-        [&](int r, int f, float v) { Ds[r * Fs + f] = v; });
-    __syncthreads();
-    gat_scores(Ws, Fs, as, ad, F, labels, mode, o, n, nr, ss, ts, lab, Ds, rsum);
-    __syncthreads();
-    if (epi == 2) {   // d hp = (dy - softmax(y) sum(dy)) * ELU'(hp)
-      stage_block(
-          n, F, n, F,
-          [&](int r, int f) {
-            const size_t row = (size_t)(o + r);
-            return (Ds[r * Fs + f] - expf(y[row * F + f]) * rsum[r]) * elu_grad(hp[row * HF + c0 + f]);
-          },
-          [&](int r, int f, float v) { Ds[r * Fs + f] = v; });
-      __syncthreads();
-    }
-    for (int rb = wave; rb < nrb; rb += kGatWaves) {
-      float sv[4], lv[4];
-      bool iv[4];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int i = 16 * rb + 4 * q + v;
-        iv[v] = i < n;
-        sv[v] = ss[i];
-        lv[v] = lab[i];
-      }
-      float tj[NJT], att[NJT][4];
-      float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-      for (int jt = 0; jt < NJT; ++jt) {
-        const int j = 16 * jt + r16;
-        const bool jv = jt < nrb && j < n;
-        tj[jt] = jt < nrb ? ts[j] : 0.f;
-        const float lj = jt < nrb ? lab[j] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int i = 16 * rb + 4 * q + v;
-          const bool edge = jv && iv[v] && (mode == 1 || i == j || (lv[v] != 0.f && lv[v] == lj));
-          att[jt][v] = edge ? lrelu(sv[v] + tj[jt], alpha) : -INFINITY;
-          mx[v] = fmaxf(mx[v], att[jt][v]);
-        }
-      }
-      float inv[4];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) mx[v] = fmaxf(mx[v], __shfl_xor(mx[v], o2));
-        float sum = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-          const float e = att[jt][v] == -INFINITY ? 0.f : expf(att[jt][v] - mx[v]);
-          att[jt][v] = e;
-          sum += e;
-        }
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) sum += __shfl_xor(sum, o2);
-        inv[v] = iv[v] ? 1.f / sum : 0.f;
-      }
-#pragma unroll
-      for (int jt = 0; jt < NJT; ++jt)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) att[jt][v] *= inv[v];
-      // datt_ij = dhp_i . Wh_j
-      floatx4 da[NJT];
-#pragma unroll
-      for (int jt = 0; jt < NJT; ++jt) da[jt] = floatx4{0.f, 0.f, 0.f, 0.f};
-      const float* Dr = Ds + (16 * rb + r16) * Fs + q;
-      for (int k = 0; k < F4; k += 4) {
-        const float av = Dr[k];
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt)
-          if (jt < nrb) da[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Ws[(16 * jt + r16) * Fs + k + q], da[jt], 0, 0, 0);
-      }
-      float dot[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int jt = 0; jt < NJT; ++jt)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) dot[v] = fmaf(att[jt][v], da[jt][v], dot[v]);
-      float dsr[4];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) dot[v] += __shfl_xor(dot[v], o2);
-        dsr[v] = 0.f;
-      }
-#pragma unroll
-      for (int jt = 0; jt < NJT; ++jt) {
-        if (jt < nrb) {
-          float cp = 0.f;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const float de = att[jt][v] * (da[jt][v] - dot[v]);
-            const float dz = (sv[v] + tj[jt]) > 0.f ? de : alpha * de;
-            dsr[v] += dz;
-            cp += dz;
-            At[(16 * rb + 4 * q + v) * Na + 16 * jt + r16] = att[jt][v];
-          }
-          cp += __shfl_xor(cp, 16);
-          cp += __shfl_xor(cp, 32);
-          if (q == 0) dtp[rb * nmax + 16 * jt + r16] = cp;
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-#pragma unroll
-        for (int o2 = 1; o2 < 16; o2 <<= 1) dsr[v] += __shfl_xor(dsr[v], o2);
-        if (r16 == 0) dss[16 * rb + 4 * q + v] = dsr[v];
-      }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < nr; j += kGatThreads) {
-      float acc = 0.f;
-      for (int rb = 0; rb < nrb; ++rb) acc += dtp[rb * nmax + j];
-      dts[j] = acc;
-      if (j < n && ds_out) {
-        ds_out[(size_t)(o + j) * heads + hd] = dss[j];
-        dt_out[(size_t)(o + j) * heads + hd] = acc;
-      }
-    }
-    __syncthreads();
-    // parameter-gradient partials of this (segment, head): LDS reads only
-    for (int c = threadIdx.x; c < 3 * F; c += kGatThreads) {
-      if (c < 2 * F) {
-        if (pda) {
-          const int f = c < F ? c : c - F;
-          const float* wv = c < F ? dss : dts;
-          float acc = 0.f;
-          for (int i = 0; i < n; ++i) acc = fmaf(Ws[i * Fs + f], wv[i], acc);
-          pda[(size_t)gh * 2 * F + c] = acc;
-        }
-      } else if (pdb) {
-        const int f = c - 2 * F;
-        double acc = 0.0;
-        for (int i = 0; i < n; ++i) acc += (double)Ds[i * Fs + f];
-        pdb[(size_t)gh * F + f] = acc;
-      }
-    }
-    // dWh_j = sum_i att_ij dhp_i + ds_j a_src + dt_j a_dst
-    for (int jb = wave; jb < nrb; jb += kGatWaves) {
-      for (int ct = 0; ct < nct; ++ct) {
-        const int fb = min(16 * ct + r16, F - 1);
-        floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
-        for (int m = 0; m < nr; m += 4)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(At[(m + q) * Na + 16 * jb + r16], Ds[(m + q) * Fs + fb], acc, 0,
-                                                     0, 0);
-        const int f = 16 * ct + r16;
-        if (f < F) {
-          const float sf = as[f], df = ad[f];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int j = 16 * jb + 4 * q + v;
-            if (j < n) dWh[(size_t)(o + j) * HF + c0 + f] = acc[v] + (dss[j] * sf + dts[j] * df);
-          }
-        }
-      }
-    }
-    __syncthreads();  // LDS reused by the next segment
-  }
-}
-
 // da_src / da_dst (heads x F each) and dbias (F, summed over the heads) from
 // the (segment, head) partials of gat_bwd_kernel: one workgroup per output,
 // a fixed-order fp64 tree over the segments
@@ -645,7 +392,7 @@ static int gat_grid(int nseg, int heads) {
 static int gat_fwd_launch(const char* who, const float* Wh, int heads, const float* as, const float* ad, int lda,
                           const float* bias, const float* labels, const int32_t* seg_off, int nseg, int n, int F,
                           float alpha, int mask_mode, int epilogue, int max_seg, float* hp, float* y, int ldy,
-                          void* stream) {
+                          void* stream, const DropArgs* drop = nullptr) {
   int rc = gat_args_ok(who, Wh, heads, as, labels, seg_off, nseg, n, F, mask_mode, epilogue, max_seg);
   if (rc) return rc;
   SGG_CHECK_ARG(ad, "%s: null a_dst", who);
@@ -653,6 +400,14 @@ static int gat_fwd_launch(const char* who, const float* Wh, int heads, const flo
   SGG_CHECK_ARG(ldy >= heads * F, "%s: ldy < heads * F", who);
   SGG_CHECK_ARG(epilogue != 2 || ldy == F, "%s: log_softmax epilogue needs a dense y (ldy == F)", who);
   if (nseg == 0 && n == 0) return 0;   // (rows but no segments: the kernel zeroes the rows)
+  if (drop) {
+    auto kd = max_seg <= 32 ? gat_fwd_drop_kernel<8> : max_seg <= 64 ? gat_fwd_drop_kernel<16>
+                                                                       : gat_fwd_drop_kernel<32>;
+    hipLaunchKernelGGL(kd, dim3(gat_grid(nseg, heads)), dim3(kGatThreads), gat_fwd_lds(F, max_seg),
+                       (hipStream_t)stream, Wh, heads, as, ad, lda, bias, labels, seg_off, nseg, n, F, alpha,
+                       mask_mode, epilogue, max_seg, hp, y, ldy, *drop);
+    SGG_RETURN_LAUNCH(who);
+  }
   auto k = max_seg <= 32 ? gat_fwd_kernel<8> : max_seg <= 64 ? gat_fwd_kernel<16> : gat_fwd_kernel<32>;
   hipLaunchKernelGGL(k, dim3(gat_grid(nseg, heads)), dim3(kGatThreads), gat_fwd_lds(F, max_seg), (hipStream_t)stream,
                      Wh, heads, as, ad, lda, bias, labels, seg_off, nseg, n, F, alpha, mask_mode, epilogue, max_seg,
@@ -663,7 +418,8 @@ static int gat_fwd_launch(const char* who, const float* Wh, int heads, const flo
 static int gat_bwd_launch(const char* who, const float* Wh, int heads, const float* as, const float* ad, int lda,
                           const float* labels, const int32_t* seg_off, int nseg, int n, int F, float alpha,
                           int mask_mode, int epilogue, int max_seg, const float* hp, const float* y, const float* dy,
-                          int lddy, float* dWh, float* ds, float* dt, float* pda, double* pdb, void* stream) {
+                          int lddy, float* dWh, float* ds, float* dt, float* pda, double* pdb, void* stream,
+                          const DropArgs* drop = nullptr) {
   int rc = gat_args_ok(who, Wh, heads, as, labels, seg_off, nseg, n, F, mask_mode, epilogue, max_seg);
   if (rc) return rc;
   SGG_CHECK_ARG(ad && dy && dWh, "%s: null pointer", who);
@@ -673,6 +429,14 @@ static int gat_bwd_launch(const char* who, const float* Wh, int heads, const flo
   if (nseg == 0 && n == 0) return 0;
   const size_t lds = gat_bwd_lds(F, max_seg);
   SGG_CHECK_ARG(lds <= 160 * 1024, "%s: segment %d x F %d needs %zu B of LDS", who, max_seg, F, lds);
+  if (drop) {
+    auto kd = max_seg <= 32 ? gat_bwd_drop_kernel<2> : max_seg <= 64 ? gat_bwd_drop_kernel<4>
+                                                                      : gat_bwd_drop_kernel<8>;
+    hipLaunchKernelGGL(kd, dim3(gat_grid(nseg, heads)), dim3(kGatThreads), lds, (hipStream_t)stream, Wh, heads, as,
+                       ad, lda, labels, seg_off, nseg, n, F, alpha, mask_mode, epilogue, max_seg, hp, y, dy, lddy,
+                       dWh, ds, dt, pda, pdb, *drop);
+    SGG_RETURN_LAUNCH(who);
+  }
   auto k = max_seg <= 32 ? gat_bwd_kernel<2> : max_seg <= 64 ? gat_bwd_kernel<4> : gat_bwd_kernel<8>;
   hipLaunchKernelGGL(k, dim3(gat_grid(nseg, heads)), dim3(kGatThreads), lds, (hipStream_t)stream, Wh, heads, as, ad,
                      lda, labels, seg_off, nseg, n, F, alpha, mask_mode, epilogue, max_seg, hp, y, dy, lddy, dWh, ds,
@@ -727,6 +491,58 @@ extern "C" int sgg_gat_bwd_ex(const float* Wh, int heads, const float* a_src, co
   // (no segments: the reduce writes zero gradients)
   gat_param_reduce(pda, pdb, nseg, heads, F, da_src, da_dst, dbias, (hipStream_t)stream);
   SGG_RETURN_LAUNCH("sgg_gat_bwd_ex");
+}
+
+// the dropout arguments of an entry point -> DropArgs (thr / scale computed
+// here, once); the limits of the mask contract (include/sgg.h)
+static int gat_drop_args(const char* who, float p, unsigned long long seed, unsigned offset, unsigned site,
+                         unsigned head0, int heads, const unsigned long long* rng_dev, DropArgs* out) {
+  SGG_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+  SGG_CHECK_ARG(site < (1u << 24), "%s: dropout site %u is not below 2^24", who, site);
+  SGG_CHECK_ARG(head0 < 256u && head0 + (unsigned)heads <= 256u, "%s: dropout heads %u + %d above 256", who, head0,
+                heads);
+  SGG_CHECK_ARG(((uintptr_t)rng_dev & 7) == 0, "%s: rng_dev must be 8-byte aligned", who);
+  *out = DropArgs{seed, rng_dev, offset, site, head0, drop_threshold(p), drop_scale(p)};
+  return 0;
+}
+
+extern "C" int sgg_gat_fwd_drop(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                                const float* bias, const float* labels, const int32_t* seg_off, int nseg, int n,
+                                int F, float alpha, int mask_mode, int epilogue, int max_seg, float* hp, float* y,
+                                int ldy, float p, unsigned long long seed, unsigned offset, unsigned site,
+                                unsigned head0, const unsigned long long* rng_dev, void* stream) {
+  const char* who = "sgg_gat_fwd_drop";
+  SGG_CHECK_ARG(heads >= 1 && lda >= F, "%s: lda < F", who);
+  DropArgs d;
+  if (int rc = gat_drop_args(who, p, seed, offset, site, head0, heads, rng_dev, &d)) return rc;
+  return gat_fwd_launch(who, Wh, heads, a_src, a_dst, lda, bias, labels, seg_off, nseg, n, F, alpha, mask_mode,
+                        epilogue, max_seg, hp, y, ldy, stream, &d);
+}
+
+extern "C" int sgg_gat_bwd_drop(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                                const float* labels, const int32_t* seg_off, int nseg, int n, int F, float alpha,
+                                int mask_mode, int epilogue, int max_seg, const float* hp, const float* y,
+                                const float* dy, int lddy, float* dWh, float* ds, float* dt, float* da_src,
+                                float* da_dst, float* dbias, void* work, float p, unsigned long long seed,
+                                unsigned offset, unsigned site, unsigned head0, const unsigned long long* rng_dev,
+                                void* stream) {
+  const char* who = "sgg_gat_bwd_drop";
+  SGG_CHECK_ARG(heads >= 1 && lda >= F, "%s: lda < F", who);
+  SGG_CHECK_ARG((ds != nullptr) == (dt != nullptr), "%s: ds and dt go together", who);
+  SGG_CHECK_ARG((da_src != nullptr) == (da_dst != nullptr) && (!dbias || da_src),
+                "%s: da_src, da_dst (and dbias) go together", who);
+  SGG_CHECK_ARG(!da_src || (work && ((uintptr_t)work & 15) == 0), "%s: da_src needs a 16-byte aligned work", who);
+  DropArgs d;
+  if (int rc = gat_drop_args(who, p, seed, offset, site, head0, heads, rng_dev, &d)) return rc;
+  float* pda = da_src ? reinterpret_cast<float*>(work) : nullptr;
+  double* pdb = dbias ? reinterpret_cast<double*>(reinterpret_cast<char*>(work) + gat_pda_bytes(nseg, heads, F))
+                      : nullptr;
+  int rc = gat_bwd_launch(who, Wh, heads, a_src, a_dst, lda, labels, seg_off, nseg, n, F, alpha, mask_mode, epilogue,
+                          max_seg, hp, y, dy, lddy, dWh, ds, dt, pda, pdb, stream, &d);
+  if (rc || !da_src) return rc;
+  // (no segments: the reduce writes zero gradients)
+  gat_param_reduce(pda, pdb, nseg, heads, F, da_src, da_dst, dbias, (hipStream_t)stream);
+  SGG_RETURN_LAUNCH(who);
 }
 
 extern "C" size_t sgg_gat_layer_lds_bytes(int K, int F, int max_seg) {

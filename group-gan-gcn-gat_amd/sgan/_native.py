@@ -22,6 +22,8 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _p = ctypes.c_void_p
 _sz = ctypes.c_size_t
+_u = ctypes.c_uint
+_u64 = ctypes.c_ulonglong
 
 MAX_HEADS = 4   # SGG_GATENC_MAX_HEADS
 
@@ -174,6 +176,11 @@ SIGNATURES = {
     "sgg_gat_fwd_wide": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _i, _p, _p]),
     "sgg_gat_bwd_wide": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p,
                               _p, _p, _p, _p]),
+    "sgg_gat_fwd_drop": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _i,
+                              _f, _u64, _u, _u, _u, _p, _p]),
+    "sgg_gat_bwd_drop": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p,
+                              _p, _p, _p, _f, _u64, _u, _u, _u, _p, _p]),
+    "sgg_dropout": (_i, [_p, _i, _i, _i, _f, _u64, _u, _u, _p, _p, _i, _p]),
     "sgg_gat_layer_lds_bytes": (_sz, [_i, _i, _i]),
     "sgg_gat_layer_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _p, _p,
                                _p, _p, _p, _i, _p]),

@@ -1538,6 +1538,114 @@ def pool_u_spec(pool):
 
 
 # ---------------------------------------------------------------------------
+# dropout masks (include/sgg.h "Dropout masks", csrc/dropout_common.h)
+# ---------------------------------------------------------------------------
+def philox4x32_10_host(counter, key):
+    """Philox4x32-10 in numpy: counter = 4 and key = 2 uint32 values or arrays
+    (broadcast together) -> the 4 output words (uint32 arrays)."""
+    import numpy as np
+    c = [np.asarray(v, dtype=np.uint64) & 0xFFFFFFFF for v in counter]
+    k = [np.asarray(v, dtype=np.uint64) & 0xFFFFFFFF for v in key]
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]       # 32 x 32 -> 64 bits: exact in uint64
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k[1], p0 & 0xFFFFFFFF]
+        k = [(k[0] + 0x9E3779B9) & 0xFFFFFFFF, (k[1] + 0xBB67AE85) & 0xFFFFFFFF]
+    return [v.astype(np.uint32) for v in c]
+
+
+def dropout_thr_scale_host(p):
+    """(thr, scale) of the keep rule as the entry points compute them from a
+    float p in [0, 1): keep iff word >= thr; a kept value is times scale."""
+    import numpy as np
+    p = np.float32(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p=%r outside [0, 1)" % float(p))
+    return np.uint32(int(float(p) * 4294967296.0)), np.float32(1.0) / (np.float32(1.0) - p)
+
+
+def dropout_keep_host(p, seed, offset, site, head, rows, cols):
+    """The kernels' dropout mask on the host (tests, debugging): the boolean
+    keep decisions of the elements rows x cols -- rows: row indices in the
+    whole node array, cols: in-segment columns (attention) or feature columns
+    -- as a (len(rows), len(cols)) array."""
+    import numpy as np
+    thr, _ = dropout_thr_scale_host(p)
+    rows = np.asarray(rows, dtype=np.uint64).reshape(-1, 1)
+    cols = np.asarray(cols, dtype=np.uint64).reshape(1, -1)
+    if site >= 1 << 24 or head >= 256:
+        raise ValueError("dropout site %d / head %d outside the counter's fields" % (site, head))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10_host((rows >> np.uint64(2), cols, (site << 8) | head, int(offset) & 0xFFFFFFFF),
+                           (seed & 0xFFFFFFFF, seed >> 32))
+    w = np.stack(np.broadcast_arrays(*w), 0)                 # word, row, col
+    sel = np.broadcast_to((rows & np.uint64(3)).astype(np.int64), w.shape[1:])
+    return np.take_along_axis(w, sel[None], 0)[0] >= thr
+
+
+class DropoutRng:
+    """The (seed, offset) source of the dropout masks.  seed: the torch seed
+    (torch.initial_seed(), read at every draw, so torch.manual_seed governs
+    it) unless one is given; offset: a 32-bit counter that next() advances.
+    Nothing is drawn from a torch generator: the noise and label-smoothing
+    streams of a run do not move when dropout is switched on."""
+
+    def __init__(self, seed=None, offset=0):
+        self.seed, self.offset = seed, int(offset) & 0xFFFFFFFF
+
+    def next(self):
+        """-> (seed, offset) of one module forward."""
+        seed = torch.initial_seed() if self.seed is None else self.seed
+        off = self.offset
+        self.offset = (off + 1) & 0xFFFFFFFF
+        return int(seed) & 0xFFFFFFFFFFFFFFFF, off
+
+
+DROPOUT_RNG = DropoutRng()   # the modules' source; a test may put its own here
+
+
+def _drop_check(drop, max_seg=0):
+    """drop = (p, seed, offset, site, head0), checked before any launch."""
+    from .scene import SGG_GAT_MAX_NODES
+    p = float(drop[0])
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p=%r outside [0, 1)" % p)
+    if max_seg > SGG_GAT_MAX_NODES:
+        raise NotImplementedError("attention dropout: a segment of %d nodes exceeds the bound of %d per segment "
+                                  "(SGG_GAT_MAX_NODES; the wide attention kernels have no dropout form)"
+                                  % (max_seg, SGG_GAT_MAX_NODES))
+    return p, int(drop[1]), int(drop[2]), int(drop[3]), int(drop[4])
+
+
+class _FeatDrop(torch.autograd.Function):
+    """sgg_dropout: y = keep ? x * scale : 0; the backward is the same launch on dy."""
+
+    @staticmethod
+    def run(x, drop):
+        lib = _lib()
+        x = _rows(x, "x")
+        p, seed, offset, site, _ = drop
+        y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        N.check(lib.sgg_dropout(N.ptr(x), x.stride(0), x.shape[0], x.shape[1], p, seed, offset, site, None, N.ptr(y),
+                                y.stride(0), N.stream_ptr()), "sgg_dropout")
+        return y
+
+    @staticmethod
+    def forward(ctx, x, drop):
+        ctx.drop = drop
+        return _FeatDrop.run(x, drop)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _FeatDrop.run(dy, ctx.drop), None
+
+
+def feature_dropout(x, drop):
+    """F.dropout(x, p) on an (n, C) matrix with the stateless mask: drop =
+    (p, seed, offset, site, _) (head 0, column = feature)."""
+    return _FeatDrop.apply(x, _drop_check(drop))
+
+
+# ---------------------------------------------------------------------------
 # graph attention
 # ---------------------------------------------------------------------------
 def gat_wide_nodes(max_seg):
@@ -1596,8 +1704,10 @@ def _gat_bwd_wide(wh, heads, a_src, a_dst, lda, labels, seg_off, nseg, F, alpha,
 
 class _GatAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, wh, a, bias, labels, seg_off, nseg, max_seg, alpha, mode, epi, heads):
+    def forward(ctx, wh, a, bias, labels, seg_off, nseg, max_seg, alpha, mode, epi, heads, drop=None):
         lib = _lib()
+        if drop is not None:
+            drop = _drop_check(drop, max_seg)
         wh = _req(wh, "wh").contiguous()
         n, HF = wh.shape
         F = HF // heads
@@ -1610,7 +1720,11 @@ class _GatAttn(torch.autograd.Function):
         y = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         hp = torch.empty(n, HF, device=wh.device, dtype=torch.float32) if epi else None
         work = None
-        if gat_wide_nodes(max_seg):
+        if drop is not None:
+            N.check(lib.sgg_gat_fwd_drop(N.ptr(wh), heads, N.ptr(a), N.ptr(a[F:]), 2 * F, N.ptr(bias), N.ptr(labels),
+                                         N.ptr(seg_off), nseg, n, F, float(alpha), mode, epi, max_seg, N.ptr(hp),
+                                         N.ptr(y), HF, *drop, None, N.stream_ptr()), "sgg_gat_fwd_drop")
+        elif gat_wide_nodes(max_seg):
             work = _gat_fwd_wide(wh, heads, a, a[F:], 2 * F, bias, labels, seg_off, nseg, F, float(alpha), mode, epi,
                                  max_seg, hp, y)
         else:
@@ -1618,6 +1732,7 @@ class _GatAttn(torch.autograd.Function):
                                     float(alpha), mode, epi, max_seg, N.ptr(hp), N.ptr(y), HF, N.stream_ptr()),
                     "sgg_gat_fwd")
         ctx.meta = (labels, seg_off, nseg, max_seg, float(alpha), mode, epi, heads, bias is not None)
+        ctx.drop = drop
         ctx.save_for_backward(wh, a, hp, y, work)
         return y
 
@@ -1632,7 +1747,12 @@ class _GatAttn(torch.autograd.Function):
         dWh = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         ds = torch.empty(n, heads, device=wh.device, dtype=torch.float32)
         dt = torch.empty(n, heads, device=wh.device, dtype=torch.float32)
-        if work is not None:
+        if ctx.drop is not None:
+            N.check(lib.sgg_gat_bwd_drop(N.ptr(wh), heads, N.ptr(a), N.ptr(a[F:]), 2 * F, N.ptr(labels),
+                                         N.ptr(seg_off), nseg, n, F, alpha, mode, epi, max_seg, N.ptr(hp), N.ptr(y),
+                                         N.ptr(dy), HF, N.ptr(dWh), N.ptr(ds), N.ptr(dt), None, None, None, None,
+                                         *ctx.drop, None, N.stream_ptr()), "sgg_gat_bwd_drop")
+        elif work is not None:
             _gat_bwd_wide(wh, heads, a, a[F:], 2 * F, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y, dy,
                           dWh, ds, dt, None, None, None, work)
         else:
@@ -1640,7 +1760,7 @@ class _GatAttn(torch.autograd.Function):
                                     epi, max_seg, N.ptr(hp), N.ptr(y), N.ptr(dy), HF, N.ptr(dWh), N.ptr(ds), N.ptr(dt),
                                     N.stream_ptr()), "sgg_gat_bwd")
         if not ctx.needs_input_grad[1] and not has_bias:
-            return dWh, None, None, None, None, None, None, None, None, None, None
+            return dWh, None, None, None, None, None, None, None, None, None, None, None
         dsdt = torch.cat([ds, dt], 1)                                       # n x [ds_h | dt_h]
         if heads == 1:
             da = xtw(wh, dsdt).t().reshape(ctx.a_shape)
@@ -1654,7 +1774,7 @@ class _GatAttn(torch.autograd.Function):
             # a near-cancelling sum (the next layer's instance norm removes
             # each feature's mean over the scene): accumulated in fp64
             dbias = dpre.view(n, heads, F).double().sum((0, 1)).float()
-        return dWh, da, dbias, None, None, None, None, None, None, None, None
+        return dWh, da, dbias, None, None, None, None, None, None, None, None, None
 
 
 class _GatAttnEx(torch.autograd.Function):
@@ -1664,8 +1784,10 @@ class _GatAttnEx(torch.autograd.Function):
     reductions)."""
 
     @staticmethod
-    def forward(ctx, wh, a_src, a_dst, bias, labels, seg_off, nseg, max_seg, alpha, mode, epi, heads):
+    def forward(ctx, wh, a_src, a_dst, bias, labels, seg_off, nseg, max_seg, alpha, mode, epi, heads, drop=None):
         lib = _lib()
+        if drop is not None:
+            drop = _drop_check(drop, max_seg)
         wh = _req(wh, "wh").contiguous()
         n, HF = wh.shape
         F = HF // heads
@@ -1677,7 +1799,11 @@ class _GatAttnEx(torch.autograd.Function):
         y = torch.empty(n, HF, device=wh.device, dtype=torch.float32)
         hp = torch.empty(n, HF, device=wh.device, dtype=torch.float32) if epi else None
         work = None
-        if gat_wide_nodes(max_seg):
+        if drop is not None:
+            N.check(lib.sgg_gat_fwd_drop(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), F, N.ptr(bias), N.ptr(labels),
+                                         N.ptr(seg_off), nseg, n, F, float(alpha), mode, epi, max_seg, N.ptr(hp),
+                                         N.ptr(y), HF, *drop, None, N.stream_ptr()), "sgg_gat_fwd_drop")
+        elif gat_wide_nodes(max_seg):
             work = _gat_fwd_wide(wh, heads, a_src, a_dst, F, bias, labels, seg_off, nseg, F, float(alpha), mode, epi,
                                  max_seg, hp, y)
         else:
@@ -1685,6 +1811,7 @@ class _GatAttnEx(torch.autograd.Function):
                                        N.ptr(seg_off), nseg, n, F, float(alpha), mode, epi, max_seg, N.ptr(hp),
                                        N.ptr(y), HF, N.stream_ptr()), "sgg_gat_fwd_ex")
         ctx.meta = (labels, seg_off, nseg, max_seg, float(alpha), mode, epi, heads, bias is not None, F)
+        ctx.drop = drop
         ctx.save_for_backward(wh, a_src, a_dst, hp, y, work)
         return y
 
@@ -1702,12 +1829,19 @@ class _GatAttnEx(torch.autograd.Function):
         if work is not None:
             _gat_bwd_wide(wh, heads, a_src, a_dst, F, labels, seg_off, nseg, F, alpha, mode, epi, max_seg, hp, y, dy,
                           dWh, None, None, da_s, da_d, dbias, work)
-            return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None
+            return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None, None
         work = torch.empty(max(16, int(lib.sgg_gat_bwd_ex_work_bytes(nseg, heads, F))), device=wh.device,
                            dtype=torch.uint8)
+        if ctx.drop is not None:
+            N.check(lib.sgg_gat_bwd_drop(N.ptr(wh), heads, N.ptr(a_src), N.ptr(a_dst), F, N.ptr(labels),
+                                         N.ptr(seg_off), nseg, n, F, alpha, mode, epi, max_seg, N.ptr(hp), N.ptr(y),
+                                         N.ptr(dy), HF, N.ptr(dWh), None, None, N.ptr(da_s), N.ptr(da_d),
+                                         N.ptr(dbias), N.ptr(work), *ctx.drop, None, N.stream_ptr()),
+                    "sgg_gat_bwd_drop")
+            return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None, None
         _gat_bwd_ex_launch(wh, heads, a_src, a_dst, labels, seg_off, nseg, n, F, alpha, mode, epi, max_seg, hp, y, dy,
                            dWh, da_s, da_d, dbias, work)
-        return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None
+        return dWh, da_s, da_d, dbias, None, None, None, None, None, None, None, None, None
 
 
 def _gat_bwd_ex_launch(wh, heads, a_src, a_dst, labels, seg_off, nseg, n, F, alpha, mode, epi, max_seg, hp, y, dy,
@@ -1729,11 +1863,11 @@ def _gat_bwd_ex_launch(wh, heads, a_src, a_dst, labels, seg_off, nseg, n, F, alp
                   6.0 * n * max_seg * HF, 4.0 * n * HF * (4 if epi else 3), launch)
 
 
-def gat_attention_ex(wh, a_src, a_dst, alpha, graph, epilogue, heads=1, bias=None):
+def gat_attention_ex(wh, a_src, a_dst, alpha, graph, epilogue, heads=1, bias=None, drop=None):
     """gat_attention with a_src / a_dst separate (heads x F each, any shape
     of that size) and the parameter gradients finished in the kernels."""
     return _GatAttnEx.apply(wh, a_src, a_dst, bias, graph.labels, graph.seg_off, graph.nseg, graph.max_seg, alpha,
-                            graph.mode, epilogue, heads)
+                            graph.mode, epilogue, heads, drop)
 
 
 class _GatLayer(torch.autograd.Function):
@@ -1909,13 +2043,16 @@ def gat_layer(x, w, a_src, a_dst, bias, graph, epilogue, eps=1e-5, alpha=0.2):
                            epilogue, torch.is_grad_enabled())
 
 
-def gat_attention(wh, a, alpha, graph, epilogue, heads=1, bias=None):
+def gat_attention(wh, a, alpha, graph, epilogue, heads=1, bias=None, drop=None):
     """Masked-softmax attention + aggregation + epilogue over `graph`
     (a SegmentGraph).  epilogue: 0 none, 1 ELU, 2 log_softmax(ELU).
     Multi-head: wh is n x heads*F, a is heads x 2F, bias (F) shared by the
-    heads and added before the epilogue (sgangat GAT, GAT.py:6-55 text)."""
+    heads and added before the epilogue (sgangat GAT, GAT.py:6-55 text).
+    drop = (p, seed, offset, site, head0): attention dropout with the
+    stateless mask (sgg_gat_fwd_drop / _bwd_drop; segments of at most
+    SGG_GAT_MAX_NODES nodes); None: no dropout, the launches as before."""
     return _GatAttn.apply(wh, a, bias, graph.labels, graph.seg_off, graph.nseg, graph.max_seg, alpha, graph.mode,
-                          epilogue, heads)
+                          epilogue, heads, drop)
 
 
 class _GatEnc(torch.autograd.Function):

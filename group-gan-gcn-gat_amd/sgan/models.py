@@ -225,6 +225,16 @@ class PoolHiddenNet(nn.Module):
 # ---------------------------------------------------------------------------
 # GAT (models.py:184-294) -> sgg_xw + sgg_gat_*
 # ---------------------------------------------------------------------------
+def _dropout_segment_check(max_seg):
+    """Dropout in training: the attention kernels with a dropout form hold a
+    segment LDS-resident.  Raises before any launch."""
+    from .scene import SGG_GAT_MAX_NODES
+    if max_seg > SGG_GAT_MAX_NODES:
+        raise NotImplementedError("dropout1 > 0 in training: a segment of %d nodes exceeds the bound of %d per segment "
+                                  "(SGG_GAT_MAX_NODES; the wide attention kernels have no dropout form)"
+                                  % (max_seg, SGG_GAT_MAX_NODES))
+
+
 class GraphAttentionLayer(nn.Module):
     def __init__(self, in_features, out_features, dropout, alpha, concat=True):
         super().__init__()
@@ -238,14 +248,19 @@ class GraphAttentionLayer(nn.Module):
         self.a = nn.Parameter(torch.empty(size=(2 * out_features, 1)))
         nn.init.xavier_uniform_(self.a.data, gain=1.414)
 
-    def forward(self, h, graph, epilogue=None):
+    def forward(self, h, graph, epilogue=None, drop=None):
         """graph: kernels.SegmentGraph.  epilogue defaults to ELU when concat
-        (models.py:207-210); GAT passes 2 to fuse its ELU + log_softmax."""
-        if self.dropout > 0 and self.training:
-            raise NotImplementedError("attention dropout is not implemented in the fused kernel (dropout1=0)")
-        wh = K.xw(h, self.W)
+        (models.py:207-210); GAT passes 2 to fuse its ELU + log_softmax.
+        drop = (seed, offset, site, head): the attention dropout's mask in
+        training (models.py:205); called alone, the layer draws its own
+        (site 0, head 0)."""
         epi = (1 if self.concat else 0) if epilogue is None else epilogue
-        return K.gat_attention(wh, self.a, self.alpha, graph, epi)
+        if not (self.dropout > 0 and self.training):
+            return K.gat_attention(K.xw(h, self.W), self.a, self.alpha, graph, epi)
+        _dropout_segment_check(graph.max_seg)
+        if drop is None:
+            drop = K.DROPOUT_RNG.next() + (0, 0)
+        return K.gat_attention(K.xw(h, self.W), self.a, self.alpha, graph, epi, drop=(self.dropout,) + tuple(drop))
 
 
 class GAT(nn.Module):
@@ -258,12 +273,25 @@ class GAT(nn.Module):
             self.add_module("attention_{}".format(i), attention)
         self.out_att = GraphAttentionLayer(nhid * nheads, nclass, dropout=dropout, alpha=alpha, concat=False)
 
-    def forward(self, x, graph):
+    def forward(self, x, graph, rng=None, site0=0):
         """models.py:231-237: heads (ELU) concatenated -> out_att -> ELU ->
-        log_softmax(dim=1); the last two fused into the kernel epilogue."""
-        heads = [att(x, graph) for att in self.attentions]
+        log_softmax(dim=1); the last two fused into the kernel epilogue.
+        In training with dropout > 0 (rng = (seed, offset) of this forward,
+        drawn here when the caller gives none): feature dropout of x (site
+        site0), the heads' attention dropout (site0 + 1, head = the head's
+        index), feature dropout of the concatenated heads (site0 + 2) and
+        out_att's attention dropout (site0 + 3), models.py:233-236."""
+        if not (self.dropout > 0 and self.training):
+            heads = [att(x, graph) for att in self.attentions]
+            x = heads[0] if len(heads) == 1 else torch.cat(heads, dim=1)
+            return self.out_att(x, graph, epilogue=2)
+        _dropout_segment_check(graph.max_seg)
+        seed, off = rng if rng is not None else K.DROPOUT_RNG.next()
+        x = K.feature_dropout(x, (self.dropout, seed, off, site0, 0))
+        heads = [att(x, graph, drop=(seed, off, site0 + 1, i)) for i, att in enumerate(self.attentions)]
         x = heads[0] if len(heads) == 1 else torch.cat(heads, dim=1)
-        return self.out_att(x, graph, epilogue=2)
+        x = K.feature_dropout(x, (self.dropout, seed, off, site0 + 2, 0))
+        return self.out_att(x, graph, epilogue=2, drop=(seed, off, site0 + 3, 0))
 
 
 class GATEncoder(nn.Module):
@@ -298,6 +326,9 @@ class GATEncoder(nn.Module):
             h_states, x2 = h_states
         sc = _scenes(seq_start_end, h_states.device, scenes)
         K.gat_wide_nodes(sc.max_n)   # a scene above the attention bound: ValueError before any launch
+        dropping = self.gat_intra.dropout > 0 and self.training
+        if dropping:
+            _dropout_segment_check(sc.max_n)
         nh = len(self.gat_intra.attentions)
         params = self.fused_params()
         need_grad = torch.is_grad_enabled() and (h_states.requires_grad or (x2 is not None and x2.requires_grad)
@@ -313,9 +344,11 @@ class GATEncoder(nn.Module):
         g = sc.groups(end_group.reshape(-1))
         intra_graph = K.SegmentGraph(sc.scene_off, sc.S, sc.max_n, 0, g.labels)
         inter_graph = K.SegmentGraph(g.group_off, sc.S, sc.max_n, 1, None)
-        intra = self.gat_intra(h_states, intra_graph)                 # B x 16
+        # one (seed, offset) per forward; gat_intra's dropout sites are 0..3, gat_inter's 4..7
+        rng = K.DROPOUT_RNG.next() if dropping else None
+        intra = self.gat_intra(h_states, intra_graph, rng=rng, site0=0)   # B x 16
         gin = K.group_mean(intra, g)                                   # R @ intra  (cap x 16)
-        gout = self.gat_inter(gin, inter_graph)                        # cap x 16
+        gout = self.gat_inter(gin, inter_graph, rng=rng, site0=4)      # cap x 16
         inter = K.group_unpool(gout, g, scale=True)                    # R^T @ gout (B x 16)
         return K.linear(torch.cat([intra, inter], dim=1), self.out_embedding)
 
@@ -349,13 +382,22 @@ class BatchMultiHeadGraphAttention(nn.Module):
         nn.init.xavier_uniform_(self.a_src, gain=1.414)
         nn.init.xavier_uniform_(self.a_dst, gain=1.414)
 
-    def forward(self, x, graph, epilogue):
-        if self.dropout.p > 0 and self.training:
-            raise NotImplementedError("attention dropout is not implemented in the fused kernel (dropout1=0)")
+    def forward(self, x, graph, epilogue, drop=None):
+        """drop = (seed, offset, site): the attention dropout's mask in
+        training (GAT.py:38 text; launch head h is the mask's head h);
+        called alone, the layer draws its own (site 0)."""
         H, Fi, Fo = self.n_head, self.f_in, self.f_out
         w_all = self.w.permute(1, 0, 2).reshape(Fi, H * Fo)                 # [w_0 | .. | w_{H-1}]
+        if self.dropout.p > 0 and self.training:
+            _dropout_segment_check(graph.max_seg)
+            if drop is None:
+                drop = K.DROPOUT_RNG.next() + (0,)
+            drop = (self.dropout.p,) + tuple(drop) + (0,)
+        else:
+            drop = None
         wh = K.xw(x, w_all)                                                  # n x H*Fo
-        return K.gat_attention_ex(wh, self.a_src, self.a_dst, 0.2, graph, epilogue, heads=H, bias=self.bias)
+        return K.gat_attention_ex(wh, self.a_src, self.a_dst, 0.2, graph, epilogue, heads=H, bias=self.bias,
+                                  drop=drop)
 
     def __repr__(self):
         return "%s (%d -> %d -> %d)" % (self.__class__.__name__, self.n_head, self.f_in, self.f_out)
@@ -381,9 +423,10 @@ class BatchGAT(nn.Module):
     def forward(self, x, graph):
         """x: (n, n_units[0]) or its two column blocks (h, pool_h).  Each layer
         is one sgg_gat_layer_fwd launch (norm + node transform + attention)
-        when it fits the kernel (LAYER_FUSED), else the per-op path."""
+        when it fits the kernel (LAYER_FUSED), else the per-op path.  In
+        training with dropout > 0: the per-op path with dropout (_forward_drop)."""
         if self.dropout > 0 and self.training:
-            raise NotImplementedError("dropout between GAT layers is not implemented (dropout1=0)")
+            return self._forward_drop(x, graph)
         for i, layer in enumerate(self.layer_stack):
             epi = 0 if i + 1 == self.n_layer else 1                          # ELU fused into the kernel
             if BatchGAT.LAYER_FUSED and K.gat_layer_ok(layer.f_in, layer.f_out, layer.n_head, graph.max_seg, epi):
@@ -395,13 +438,36 @@ class BatchGAT(nn.Module):
             x = layer(x, graph, epi)
         return x
 
+    def _forward_drop(self, x, graph):
+        """forward() in training with dropout > 0, per op (seg_instance_norm,
+        xw, gat_attention_ex with the mask): layer l's attention dropout is
+        site 2l (GAT.py:38 text), the dropout after the ELU of all but the
+        last layer site 2l + 1 (GAT.py:87 text); one (seed, offset) drawn per
+        call."""
+        _dropout_segment_check(graph.max_seg)
+        seed, off = K.DROPOUT_RNG.next()
+        if isinstance(x, tuple):
+            x = torch.cat(x, dim=1)
+        for i, layer in enumerate(self.layer_stack):
+            last = i + 1 == self.n_layer
+            x = K.seg_instance_norm(x, graph.seg_off, graph.nseg)
+            x = layer(x, graph, 0 if last else 1, drop=(seed, off, 2 * i))
+            if not last:
+                x = K.feature_dropout(x, (self.dropout, seed, off, 2 * i + 1, 0))
+        return x
+
     def forward_pair(self, xa, graph_a, xb, graph_b):
         """forward() of two batches, a without autograd (the discriminator
         step's) and b (the generator step's): layer by layer, each fused
         layer of both batches in ONE launch (kernels.gat_layer_pair,
-        sgg_gat_layer_fwd2); each result as forward() computes it."""
+        sgg_gat_layer_fwd2); each result as forward() computes it.  In
+        training with dropout > 0 the batches go one after the other through
+        the per-op path, each with an offset of its own."""
         if self.dropout > 0 and self.training:
-            raise NotImplementedError("dropout between GAT layers is not implemented (dropout1=0)")
+            _dropout_segment_check(max(graph_a.max_seg, graph_b.max_seg))
+            with torch.no_grad():
+                xa = self._forward_drop(xa, graph_a)
+            return xa, self._forward_drop(xb, graph_b)
         for i, layer in enumerate(self.layer_stack):
             epi = 0 if i + 1 == self.n_layer else 1
             ok = BatchGAT.LAYER_FUSED and all(K.gat_layer_ok(layer.f_in, layer.f_out, layer.n_head, g.max_seg, epi)

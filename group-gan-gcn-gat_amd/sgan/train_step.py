@@ -247,6 +247,15 @@ class GanTrainer:
             # context, scene sharding) changes the batch a BatchNorm averages over
             raise NotImplementedError("GanTrainer: BatchNorm layers (%s) are not supported (train.py's batch_norm=0 "
                                       "default); drive the modules with the reference's own step functions" % bn[:3])
+        gm = getattr(G, "gatencoder", None)   # GATEncoder (gat) or BatchGATEncoder (sgangat)
+        gat = getattr(gm, "gat_intra", None) or getattr(gm, "gat_net", None)
+        p1 = getattr(gat, "dropout", 0)
+        if p1 and p1 > 0:
+            # the plan computes the noise-independent context once per batch, so all
+            # best-of-k samples would share one dropout mask where train.py draws one per sample
+            raise NotImplementedError("GanTrainer: a generator with dropout1=%g is not supported (the shared G "
+                                      "context would give all best_k samples one dropout mask); drive the modules "
+                                      "with the reference's own step functions (scripts/train.py --dropout1)" % p1)
         # Adam over ALL of G's parameters, as train.py:238 builds it, so the
         # optimizer state (and its index order) matches reference checkpoints;
         # the unused graph module gets no gradient and Adam skips it

@@ -289,6 +289,74 @@ int sgg_gat_bwd_wide(const float* Wh, int heads, const float* a_src, const float
                      const float* dy, int lddy, float* dWh, float* ds, float* dt, float* da_src,
                      float* da_dst, float* dbias, float* work, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Dropout masks (attention dropout of the graph attention, models.py:205 /
+ * GAT.py:38 text; feature dropout, models.py:233, 235 / GAT.py:87 text).
+ * A mask is a pure function of (seed, offset, site, head, row, col): nothing
+ * is stored, a backward regenerates the mask of its forward from the same
+ * arguments.  The contract (csrc/dropout_common.h; sgan.kernels
+ * .dropout_keep_host restates it in numpy):
+ *   generator  Philox4x32-10: multipliers 0xD2511F53, 0xCD9E8D57, Weyl
+ *              constants 0x9E3779B9, 0xBB67AE85;
+ *   key        (seed & 0xffffffff, seed >> 32);
+ *   counter    (row >> 2, col, (site << 8) | head, offset); the element uses
+ *              output word row & 3, so four consecutive rows share one call.
+ *              row: the element's row in the whole node array (seg_off[g] + i,
+ *              not the in-segment index); col: the in-segment column j of an
+ *              attention element, the feature column of a feature element;
+ *              site: a caller-chosen id of the dropout site, below 2^24;
+ *              head: below 256 (launch head h uses head0 + h; 0 for features);
+ *              offset: a 32-bit call counter;
+ *   keep rule  keep iff word >= thr, thr = (uint32_t)((double)p * 4294967296.0);
+ *              a kept value is multiplied by scale = 1.0f / (1.0f - p), a
+ *              dropped one is exactly 0.f.  thr and scale are computed once,
+ *              in the entry point, from a float p in [0, 1): any other p is
+ *              SGG_E_ARG.  p = 0 keeps everything with scale == 1.0f.
+ * The mask never depends on a tile shape, an LDS layout, a grid size or a
+ * template instantiation.  Known answers (counter / key -> words):
+ *   (0, 0, 0, 0) / (0, 0)                -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   all ffffffff / all ffffffff          -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   (243f6a88, 85a308d3, 13198a2e, 03707344) / (a4093822, 299f31d0)
+ *                                        -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * rng_dev (every entry point below; may be NULL): two 8-byte device words
+ * {seed, offset (low 32 bits)}.  When it is not NULL the kernel reads the pair
+ * from there and ignores the by-value seed / offset, so a captured launch can
+ * be replayed with other masks.
+ *
+ * sgg_gat_fwd_drop: sgg_gat_fwd_ex with dropout of probability p on the
+ * normalised attention (att_ij <- m_ij att_ij before the aggregation); hp, y
+ * and the epilogues as there.  a_src / a_dst: head h's vectors at a_src + h *
+ * lda, a_dst + h * lda as in sgg_gat_fwd_wide (the `a` form: a, a + F, lda =
+ * 2F; the `_ex` form: lda = F).  max_seg above SGG_GAT_MAX_NODES is SGG_E_ARG
+ * (the wide kernels have no dropout form).  At p = 0 every output is bitwise
+ * sgg_gat_fwd_ex's. */
+int sgg_gat_fwd_drop(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                     const float* bias, const float* labels, const int32_t* seg_off, int nseg, int n, int F,
+                     float alpha, int mask_mode, int epilogue, int max_seg, float* hp, float* y, int ldy,
+                     float p, unsigned long long seed, unsigned offset, unsigned site, unsigned head0,
+                     const unsigned long long* rng_dev, void* stream);
+/* Backward of sgg_gat_fwd_drop (the same p, seed, offset, site, head0 /
+ * rng_dev): with att the undropped softmax (recomputed) and m the scaled mask,
+ *   datt_ij = m_ij (dhp_i . Wh_j),  de_ij = att_ij (datt_ij - sum_j att_ij datt_ij),
+ *   dWh_j = sum_i (att m)_ij dhp_i + ds_j a_src + dt_j a_dst.
+ * Always writes dWh (n x heads*F, zero past the last segment).  ds, dt (n x
+ * heads; both or neither): as sgg_gat_bwd writes them.  da_src, da_dst (heads
+ * x F; both or neither) and dbias (F; only with them): finished on the device
+ * as sgg_gat_bwd_ex does, through `work` (16-byte aligned,
+ * sgg_gat_bwd_ex_work_bytes(nseg, heads, F); may be NULL without them). */
+int sgg_gat_bwd_drop(const float* Wh, int heads, const float* a_src, const float* a_dst, int lda,
+                     const float* labels, const int32_t* seg_off, int nseg, int n, int F, float alpha,
+                     int mask_mode, int epilogue, int max_seg, const float* hp, const float* y,
+                     const float* dy, int lddy, float* dWh, float* ds, float* dt, float* da_src,
+                     float* da_dst, float* dbias, void* work, float p, unsigned long long seed,
+                     unsigned offset, unsigned site, unsigned head0, const unsigned long long* rng_dev,
+                     void* stream);
+/* Feature dropout: y[r, c] = keep ? x[r, c] * scale : 0 over rows x cols (row
+ * strides ldx, ldy >= cols; head 0, col = c).  The backward is the same call
+ * on dy.  y may be x (in place). */
+int sgg_dropout(const float* x, int ldx, int rows, int cols, float p, unsigned long long seed, unsigned offset,
+                unsigned site, const unsigned long long* rng_dev, float* y, int ldy, void* stream);
+
 /* One layer of the sgangat family's batched GAT in one launch (GAT.py:71-86
  * text): InstanceNorm1d over each segment's rows (biased variance, eps; the
  * statistics of sgg_seg_norm_fwd), Wh = xn [w_0 | .. | w_{H-1}] with w in

@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|...]"""
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|gatdrop|...]"""
 import os
 import sys
 
@@ -140,6 +140,52 @@ def gatwide(S, n, heads, F, reps=20):
             name, S, n, heads, F, uf, uf * 1e3 / pairs, ub, ub * 1e3 / pairs), flush=True)
 
 
+def gatdrop(S, n, heads, F, p=0.3, reps=2000, rounds=5):
+    """The attention kernels with dropout (sgg_gat_fwd_drop / sgg_gat_bwd_drop
+    at probability p) next to sgg_gat_fwd_ex / sgg_gat_bwd_ex on the same
+    operands (S complete-graph segments of n <= 128 nodes, ELU epilogue,
+    parameter gradients finished): the four calls alternate over `rounds`
+    windows of `reps` back-to-back launches; median (min .. max) per call."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B, HF = S * n, heads * F
+    off = torch.arange(0, B + 1, n, dtype=torch.int32, device=dev)
+    wh = torch.randn(B, HF, device=dev)
+    a_s, a_d = torch.randn(heads, F, device=dev) * 0.5, torch.randn(heads, F, device=dev) * 0.5
+    bias = torch.randn(F, device=dev) * 0.1
+    dy = torch.randn(B, HF, device=dev)
+    y, hp, dWh = (torch.empty(B, HF, device=dev) for _ in range(3))
+    da_s, da_d, db = torch.empty_like(a_s), torch.empty_like(a_d), torch.empty_like(bias)
+    lib = N.load()
+    work = torch.empty(int(lib.sgg_gat_bwd_ex_work_bytes(S, heads, F)), device=dev, dtype=torch.uint8)
+    seed, st = 0x9E3779B97F4A7C15, N.stream_ptr()
+    calls = {
+        "fwd_ex": lambda: N.check(lib.sgg_gat_fwd_ex(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), N.ptr(bias), None,
+                                                     N.ptr(off), S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), HF, st),
+                                  "fwd"),
+        "fwd_drop": lambda: N.check(lib.sgg_gat_fwd_drop(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), F, N.ptr(bias),
+                                                         None, N.ptr(off), S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y),
+                                                         HF, p, seed, 1, 0, 0, None, st), "fwd_drop"),
+        "bwd_ex": lambda: N.check(lib.sgg_gat_bwd_ex(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), None, N.ptr(off), S, B,
+                                                     F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y), N.ptr(dy), HF, N.ptr(dWh),
+                                                     N.ptr(da_s), N.ptr(da_d), N.ptr(db), N.ptr(work), st), "bwd"),
+        "bwd_drop": lambda: N.check(lib.sgg_gat_bwd_drop(N.ptr(wh), heads, N.ptr(a_s), N.ptr(a_d), F, None,
+                                                         N.ptr(off), S, B, F, 0.2, 1, 1, n, N.ptr(hp), N.ptr(y),
+                                                         N.ptr(dy), HF, N.ptr(dWh), None, None, N.ptr(da_s),
+                                                         N.ptr(da_d), N.ptr(db), N.ptr(work), p, seed, 1, 0, 0, None,
+                                                         st), "bwd_drop"),
+    }
+    us = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, c in calls.items():
+            us[k].append(timeit(c, reps))
+    pairs = float(S) * n * n * heads
+    print("gat dropout p=%.1f S=%3d n=%4d heads=%d F=%3d (%d x %d launches each)" % (p, S, n, heads, F, rounds, reps))
+    for k, v in us.items():
+        print("  %-8s %7.2f us (%.2f .. %.2f)  %6.3f ns/pair" % (k, float(np.median(v)), min(v), max(v),
+                                                                  float(np.median(v)) * 1e3 / pairs), flush=True)
+
+
 def lstm(B, T, H, decoder, reps=10, save=False):
     torch.manual_seed(0)
     dev = "cuda"
@@ -275,6 +321,10 @@ if __name__ == "__main__":
         for (S, n) in ((32, 128), (8, 256), (1, 1024)):
             for (heads, F) in ((1, 72), (4, 16)):
                 gatwide(S, n, heads, F)
+        sys.exit(0)
+    if what == "gatdrop":   # what the mask generator costs inside the resident attention kernels
+        for F in (72, 16):
+            gatdrop(64, 64, 1, F)
         sys.exit(0)
     if what == "lbwd":    # the discriminator encoder's backward with weight gradients
         for (B, T, H) in ((2560, 20, 48), (1280, 20, 48), (2560, 12, 32), (1280, 8, 32), (8192, 20, 48)):
