@@ -50,6 +50,13 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// the same shuffle tree over doubles (metrics.hip: every sum over peds is fp64)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));

@@ -257,7 +257,11 @@ SIGNATURES = {
     "sgg_l2_loss_fwd": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _i, _f, _p, _p, _p, _p]),
     "sgg_l2_loss_bwd": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _i, _f, _p, _p, _i, _p]),
     "sgg_l2_loss_bwd_scenes": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _i, _f, _p, _p, _i, _p, _p]),
+    "sgg_val_metrics_work_floats": (_sz, [_i]),
+    "sgg_val_metrics": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _f, _i, _i, _p, _p, _p]),
 }
+
+VAL_SLOTS = 11   # SGG_VAL_SLOTS
 
 _lib = None
 

@@ -1225,6 +1225,41 @@ long long sgg_gather_batch_floats(int B, int obs_len, int pred_len);
 int sgg_gather_batch(const float* table, int rec, const int32_t* rows, int B, int obs_len, int pred_len, float* out,
                      void* stream);
 
+/* ------------------------------------------------------------------------
+ * Validation metrics of one batch (scripts/train.py:487-568 check_accuracy:
+ * relative_to_abs, cal_l2_losses, cal_ade, cal_fde, the discriminator loss
+ * and the linear / non-linear ped counts) in ONE launch, ADDED into the
+ * caller's accumulator acc[SGG_VAL_SLOTS] (doubles):
+ *   0, 1     l2_loss(fake_abs, gt, mask, 'sum'), l2_loss(fake_rel, gt_rel,
+ *            mask, 'sum')                                  (losses.py:52-71)
+ *   2, 3, 4  displacement_error summed over all / linear / non-linear peds
+ *            (losses.py:74-95; linear = 1 - non_linear)
+ *   5, 6, 7  final_displacement_error, the same three ways (losses.py:98-119)
+ *   8        bce_loss(real, y_real) + bce_loss(fake, 0), each a mean over B
+ *            (losses.py:5-49 gan_d_loss); untouched when scores is NULL
+ *   9, 10    number of linear / non-linear peds (sums of 1 - non_linear,
+ *            non_linear)
+ * pred_rel, gt, gt_rel: (T x B x 2); start (B x 2) = obs_traj[-1]; mask: B
+ * rows of ld floats, element mask[p * ld + t] (the view loss_mask[:,
+ * obs_len:]); non_linear (B); scores (2 B, [fake | real]) or NULL.
+ * fake_abs[t] = start + sum_{tau <= t} pred_rel[tau], the cumulative sum
+ * formed step by step in fp32 and start added last (sgan/utils.py
+ * relative_to_abs); it is never stored.  Every element term is fp32, as the
+ * torch op it replaces; every sum is fp64 in a fixed order (a lane per ped,
+ * a shuffle tree per wave, the waves, then the workgroups' partials in index
+ * order by the last workgroup to finish): no floating-point atomics, the
+ * same input gives the same bits.  work: sgg_val_metrics_work_floats(B)
+ * floats, 8-byte aligned; its first word is the ticket of the last-arriver
+ * (zero when work is first used; every call leaves it at zero).  Calls that
+ * share work or acc must be ordered on one stream.  T >= 1, B >= 1, ld >= T;
+ * SGG_E_ARG (nothing launched, acc untouched) otherwise or for a NULL
+ * operand other than scores. */
+#define SGG_VAL_SLOTS 11
+size_t sgg_val_metrics_work_floats(int B);
+int sgg_val_metrics(const float* pred_rel, const float* gt, const float* gt_rel, const float* start,
+                    const float* mask, int ld, const float* non_linear, const float* scores, float y_real, int T,
+                    int B, double* acc, float* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|gatdrop|...]"""
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|gatdrop|...]
+validate [a|b]: wall time of one check_accuracy pass, three routes; valkernel: sgg_val_metrics alone."""
 import os
 import sys
 
@@ -282,8 +283,106 @@ def dense():
               flush=True)
 
 
+def _val_models():
+    """The default (gat) generator and discriminator, seeded random weights."""
+    from sgan.models import TrajectoryDiscriminator, TrajectoryGenerator
+    torch.manual_seed(0)
+    g = TrajectoryGenerator(8, 12, embedding_dim=16, encoder_h_dim=32, decoder_h_dim=32, mlp_dim=64,
+                            noise_dim=(8,), noise_mix_type="global", pooling_type="pool_net",
+                            pool_every_timestep=False, bottleneck_dim=8, batch_norm=False,
+                            n_units=[40, 16, 40], n_heads=1, dropout1=0.0, alpha=0.2)
+    d = TrajectoryDiscriminator(8, 12, embedding_dim=16, h_dim=48, mlp_dim=64, batch_norm=False, d_type="global")
+    return g.cuda(), d.cuda()
+
+
+class _ValArgs:
+    obs_len, pred_len, skip, delim, batch_size, loader_num_workers, num_samples_check = 8, 12, 1, "tab", 64, 0, 5000
+
+
+def validate(rounds=5, split=("zara1", "test"), only=None):
+    """One check_accuracy pass over zara1/test at batch 64, gat generator:
+    (a) the torch restatement of the reference loop (tests/_check_accuracy_ref
+        .py) on the GPU modules -- what a user of the fast trainers ran before
+        sgan.validate existed;
+    (b) sgan.validate.check_accuracy with the host DataLoader;
+    (c) the same with the device-resident loader.
+    The three alternate over `rounds` rounds in this process; wall time around
+    a final torch.cuda.synchronize().  only = "a" / "b": one pass of that
+    route and nothing else (a kernel-trace run)."""
+    import random
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _check_accuracy_ref import check_accuracy_ref
+    from sgan.data.device import device_data_loader
+    from sgan.data.loader import data_loader
+    from sgan.validate import check_accuracy
+    g, d = _val_models()
+    path = os.path.join(ROOT, "tests", "golden", "datasets_group", *split)
+    _, host = data_loader(_ValArgs, path)
+    _, dev = device_data_loader(_ValArgs, path, "cuda")
+    routes = {"a": lambda: check_accuracy_ref(_ValArgs, host, g, d, device="cuda"),
+              "b": lambda: check_accuracy(_ValArgs, host, g, d),
+              "c": lambda: check_accuracy(_ValArgs, dev, g, d)}
+
+    def timed(k):
+        torch.manual_seed(1)
+        random.seed(1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = routes[k]()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, m
+
+    if only:
+        ms, m = timed(only)   # (cold: the trace is about launch counts)
+        print("validate route %s: %d batches, %.1f ms, ade %.6f" % (only, len(host), ms, m["ade"]), flush=True)
+        return
+    for k in routes:          # warm-up: allocator, folds, dataset table
+        timed(k)
+    ms = {k: [] for k in routes}
+    for r in range(rounds):
+        vals = {}
+        for k in routes:
+            t, m = timed(k)
+            ms[k].append(t)
+            vals[k] = m
+        print("validate round %d: (a) torch restatement %8.2f ms  (b) check_accuracy %8.2f ms  (c) device loader "
+              "%8.2f ms   ade a %.6f b %.6f c %.6f" % (r, ms["a"][-1], ms["b"][-1], ms["c"][-1], vals["a"]["ade"],
+                                                        vals["b"]["ade"], vals["c"]["ade"]), flush=True)
+    print("validate medians over %d rounds, %d batches of 64 sequences: (a) %.2f ms  (b) %.2f ms  (c) %.2f ms; "
+          "(b) faster than (a) in every round: %s" % (rounds, len(host), float(np.median(ms["a"])),
+                                                      float(np.median(ms["b"])), float(np.median(ms["c"])),
+                                                      all(b < a for a, b in zip(ms["a"], ms["b"]))), flush=True)
+
+
+def valkernel(B, T=12, reps=200, rounds=5):
+    """sgg_val_metrics alone (with scores): back-to-back launches, median of `rounds` windows."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    lib = N.load()
+    pred_rel, gt, gt_rel = (torch.randn(T, B, 2, device=dev) for _ in range(3))
+    start, nl = torch.randn(B, 2, device=dev), (torch.rand(B, device=dev) < 0.4).float()
+    mask = torch.ones(B, 8 + T, device=dev)[:, 8:]
+    scores = torch.randn(2 * B, device=dev)
+    acc = torch.zeros(N.VAL_SLOTS, dtype=torch.float64, device=dev)
+    work = torch.zeros(int(lib.sgg_val_metrics_work_floats(B)), device=dev)
+    call = lambda: N.check(lib.sgg_val_metrics(N.ptr(pred_rel), N.ptr(gt), N.ptr(gt_rel), N.ptr(start), N.ptr(mask),
+                                               8 + T, N.ptr(nl), N.ptr(scores), 0.9, T, B, N.ptr(acc), N.ptr(work),
+                                               N.stream_ptr()), "sgg_val_metrics")
+    us = [timeit(call, reps) for _ in range(rounds)]
+    print("sgg_val_metrics B=%6d T=%2d  %6.2f us (%.2f .. %.2f), %d workgroups" % (
+        B, T, float(np.median(us)), min(us), max(us), (B + 255) // 256), flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "pool"
+    if what == "validate":   # the validation pass: torch restatement against sgan.validate.check_accuracy
+        validate(only=sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if what == "valkernel":  # the metrics launch alone: one real batch's peds, and the synthetic leg's
+        for B in (450, 20480):
+            valkernel(B)
+        sys.exit(0)
     if what == "big":     # one config (profiling)
         run(1280, 20, 32, 8, reps=5)
         sys.exit(0)
