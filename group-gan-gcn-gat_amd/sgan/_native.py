@@ -147,6 +147,23 @@ class BceJob(ctypes.Structure):
                 ("addend", _p), ("total", _p), ("nvalid", _p)]
 
 
+class DecStep(ctypes.Structure):
+    """SggDecStep (include/sgg.h): one forward step of the per-step pooling rollout."""
+    _fields_ = ([(n, _i) for n in ("B", "H", "bn", "mlp_dim", "NU", "mlp", "cell", "ldwu")]
+                + [(n, _p) for n in ("h_prev", "pool_prev", "c_prev", "r_in", "pos_prev",
+                                     "W1m", "b1m", "W2m", "b2m", "A", "Whh", "bias", "Wp", "bp", "Wu", "cu",
+                                     "h", "c", "rel", "pos", "U", "act", "h_mix", "z1")])
+
+
+class DecStepBwd(ctypes.Structure):
+    """SggDecStepBwd (include/sgg.h): one backward step of the per-step pooling rollout."""
+    _fields_ = ([(n, _i) for n in ("B", "H", "bn", "mlp_dim", "mlp", "cell")]
+                + [(n, _p) for n in ("dh", "dc", "drel", "dpos", "act", "c", "c_prev", "h_mix", "z1",
+                                     "W1m", "W2m", "A", "Whh", "Wp",
+                                     "dh_prev", "dpool_prev", "dc_prev", "dr_in", "dpos_prev",
+                                     "dG", "dz2", "dz1", "drel_tot")])
+
+
 # name -> (restype, argtypes); must mirror include/sgg.h exactly
 SIGNATURES = {
     "sgg_version": (_i, []),
@@ -259,6 +276,11 @@ SIGNATURES = {
     "sgg_l2_loss_bwd_scenes": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _i, _f, _p, _p, _i, _p, _p]),
     "sgg_val_metrics_work_floats": (_sz, [_i]),
     "sgg_val_metrics": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _f, _i, _i, _p, _p, _p]),
+    "sgg_dec_step_ok": (_i, [_i, _i, _i, _i]),
+    "sgg_dec_step_saved_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "sgg_dec_step_fwd": (_i, [ctypes.POINTER(DecStep), _p]),
+    "sgg_dec_step_bwd": (_i, [ctypes.POINTER(DecStepBwd), _p]),
+    "sgg_pool_dpos": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
 }
 
 VAL_SLOTS = 11   # SGG_VAL_SLOTS

@@ -6,6 +6,7 @@ all nodes (X^T dY, column sums) included (sgg_xtw, xtw.hip).  No op has a CPU
 path.
 """
 import contextlib
+import ctypes
 import functools
 import os
 import weakref
@@ -3747,3 +3748,277 @@ class _Split2(torch.autograd.Function):
 
 def split2(x, B):
     return _Split2.apply(x, B)
+
+
+# ---------------------------------------------------------------------------
+# per-step pooling decoder (pool_every_timestep = 1): the row-local step
+# kernels (sgg_dec_step_fwd / _bwd) between the pooling launches
+# ---------------------------------------------------------------------------
+def dec_step_enabled():
+    """SGG_DEC_STEP=0 keeps the per-op decoder loop (stock nn.LSTM + one
+    launch per layer); read at every call, so one process can alternate."""
+    return os.environ.get("SGG_DEC_STEP", "1") != "0"
+
+
+class _PoolPos(torch.autograd.Function):
+    """_Pool with the gradient of the positions (sgg_pool_dpos): the per-step
+    rollout pools at predicted positions (models.py:160, :164).  Same
+    arguments, pooling launches and parameter gradients as _Pool."""
+
+    @staticmethod
+    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, pdh=None):
+        return _Pool.forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, U, pdh)
+
+    @staticmethod
+    def backward(ctx, dout, _dam):
+        # the loop calls one pooling net at every step, so autograd SUMS this op's parameter gradients with
+        # the other steps': they must be written now, not at the trainer's grad_flush (defer_grad_finish's
+        # invariant -- no parameter feeds two ops -- does not hold here)
+        prev, _DEFER[0] = _DEFER[0], 0
+        try:
+            grads = list(_Pool.backward(ctx, dout, _dam))
+        finally:
+            _DEFER[0] = prev
+        if ctx.needs_input_grad[1]:
+            _h, pos, _W1, _We, _be, A, W2, U, out, am = ctx.saved_tensors
+            sc = ctx.scenes
+            B, bn = out.shape
+            dout = dout.contiguous()
+            dpos = torch.empty(B, 2, device=pos.device, dtype=torch.float32)
+            N.check(_lib().sgg_pool_dpos(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout),
+                                         N.ptr(sc.scene_off), sc.S, B, bn, N.ptr(dpos), N.stream_ptr()),
+                    "sgg_pool_dpos")
+            grads[1] = dpos
+        return tuple(grads)
+
+
+def social_pool_pos(h, pos, W1, We, be, b1, W2, b2, scenes, U=None):
+    """social_pool whose backward also returns the gradient of pos."""
+    out, _ = _PoolPos.apply(h, pos, W1, We, be, b1, W2, b2, scenes, None, U, None)
+    return out
+
+
+def dec_step_ok(H, bn, mlp_dim, NU=512):
+    """sgg_dec_step_ok: 0 = no fused step, 1 = the step with decoder.mlp on
+    sgg_xw launches, 3 = the whole step in one launch."""
+    return int(_lib().sgg_dec_step_ok(int(H), int(bn), int(mlp_dim), int(NU)))
+
+
+class DecRollout:
+    """One rollout's shared state: the weights, the stacked outputs and saved
+    states of its T steps, and the stacked operand gradients its step
+    backwards fill.  Step 0's backward -- the last to run -- forms every
+    weight gradient from the stacks (sgg_xtw over the T B rows, fixed order)
+    and returns them; the other steps take the weights from here, not as
+    autograd inputs.  mlp application m (after pooling m; inside step m + 1's
+    launch, or the tail's for m = T - 1) owns slice m of the mlp stacks."""
+
+    def __init__(self, T, B, lstm, emb, proj, mlp, u, fuse_mlp, save, dev):
+        l1, l2 = (mlp[0], mlp[2]) if fuse_mlp else (None, None)
+        H = lstm.hidden_size
+        self.T, self.B, self.H = T, B, H
+        self.fuse_mlp = fuse_mlp
+        self.D = l1.out_features if fuse_mlp else 0
+        self.bn = l1.in_features - H if fuse_mlp else 0
+        self.save = save
+        self.lstm_w = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, emb.weight, emb.bias)
+        self.Whh = lstm.weight_hh_l0.contiguous()
+        self.A, self.bias = fold_fwd(*lstm_fold_spec(lstm, emb))
+        self.Wp, self.bp = proj.weight.contiguous(), proj.bias.contiguous()
+        self.mlp_w = (l1.weight.contiguous(), l1.bias.contiguous(), l2.weight.contiguous(),
+                      l2.bias.contiguous()) if fuse_mlp else None
+        self.Wu, self.cu = u
+        assert self.Wu.stride(1) == 1 and self.cu.is_contiguous()
+        self.NU = self.Wu.shape[0]
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.h_all = torch.empty(T, B, H, **f32)
+        self.c_all = torch.empty(T, B, H, **f32)
+        self.rbuf = torch.empty(T + 1, B, 2, **f32)     # [r_in of step 0 | rel of every step]
+        self.pos_all = torch.empty(T, B, 2, **f32)
+        self.pools = [None] * T                          # pool_h of pooling m (the mlp's second input block)
+        self.tail_ran = False
+        self.want_u = True                               # False: the steps skip the U epilogue (no pooling follows)
+        D = self.D
+        if save:
+            self.act_all = torch.empty(T, B, 4 * H, **f32)
+            self.hmix_all = torch.empty(T, B, H, **f32)      # step t's h_mix (= h0 at t = 0)
+            self.hmix_tail = torch.empty(B, H, **f32) if fuse_mlp else None
+            self.z1_all = torch.empty(T, B, D, **f32) if fuse_mlp else None
+            # operand gradients: zero, so a slice whose backward never ran adds nothing
+            z = torch.zeros(T * B * (4 * H + 2 + H + D), **f32)
+            o = 0
+            self.dG_all = z[o:o + T * B * 4 * H].view(T, B, 4 * H)
+            o += T * B * 4 * H
+            self.drt_all = z[o:o + T * B * 2].view(T, B, 2)
+            o += T * B * 2
+            self.dz2_all = z[o:o + T * B * H].view(T, B, H)
+            o += T * B * H
+            self.dz1_all = z[o:o + T * B * D].view(T, B, D) if fuse_mlp else None
+        else:
+            self.act_all = self.hmix_all = self.hmix_tail = self.z1_all = None
+
+    def weights(self):
+        """The autograd inputs of step 0, in the order its backward returns their gradients."""
+        ws = list(self.lstm_w) + [self.Wp, self.bp]
+        if self.fuse_mlp:
+            ws += list(self.mlp_w)
+        return ws
+
+    def fwd(self, t, h_prev, pool_prev, c_prev, r_in, pos_prev):
+        """Launch step t (t = T: the tail, decoder.mlp alone) -> (h, c, rel, pos, U)."""
+        T, B, H = self.T, self.B, self.H
+        tail = t == T
+        mlp = self.fuse_mlp and pool_prev is not None
+        U = torch.empty(B, self.NU, device=h_prev.device, dtype=torch.float32) if self.want_u and not tail else None
+        if tail:
+            h = torch.empty(B, H, device=h_prev.device, dtype=torch.float32)
+            c = rel = pos = act = None
+            hmix = self.hmix_tail
+        else:
+            h, c, rel, pos = self.h_all[t], self.c_all[t], self.rbuf[t + 1], self.pos_all[t]
+            act = self.act_all[t] if self.save else None
+            hmix = self.hmix_all[t] if self.save else None
+        z1 = self.z1_all[t - 1] if (mlp and self.save) else None
+        W1m, b1m, W2m, b2m = self.mlp_w if mlp else (None,) * 4
+        a = N.DecStep(B, H, self.bn, self.D, self.NU, int(mlp), int(not tail), self.Wu.stride(0),
+                      N.ptr(h_prev), N.ptr(pool_prev), N.ptr(c_prev), N.ptr(r_in), N.ptr(pos_prev),
+                      N.ptr(W1m), N.ptr(b1m), N.ptr(W2m), N.ptr(b2m), N.ptr(self.A), N.ptr(self.Whh),
+                      N.ptr(self.bias), N.ptr(self.Wp), N.ptr(self.bp), N.ptr(self.Wu), N.ptr(self.cu),
+                      N.ptr(h), N.ptr(c), N.ptr(rel), N.ptr(pos), N.ptr(U), N.ptr(act), N.ptr(hmix), N.ptr(z1))
+        N.check(_lib().sgg_dec_step_fwd(ctypes.byref(a), N.stream_ptr()), "sgg_dec_step_fwd")
+        if tail:
+            self.tail_ran = True
+        return h, c, rel, pos, U
+
+    def bwd(self, t, mlp, c_prev, dh, dc, drel, dpos):
+        """Launch step t's backward -> (dh_prev, dpool_prev, dc_prev, dr_in)."""
+        T, B, H = self.T, self.B, self.H
+        tail = t == T
+        dev = self.h_all.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        dh_prev = torch.empty(B, H, **f32)
+        dpool = torch.empty(B, self.bn, **f32) if mlp else None
+        dc_prev = torch.empty(B, H, **f32) if not tail else None
+        dr_in = torch.empty(B, 2, **f32) if not tail else None
+        W1m, _b1, W2m, _b2 = self.mlp_w if mlp else (None,) * 4
+        a = N.DecStepBwd(B, H, self.bn, self.D, int(mlp), int(not tail),
+                         N.ptr(dh), N.ptr(dc), N.ptr(drel), N.ptr(dpos),
+                         N.ptr(None if tail else self.act_all[t]), N.ptr(None if tail else self.c_all[t]),
+                         N.ptr(c_prev), N.ptr(self.hmix_tail if tail else self.hmix_all[t]),
+                         N.ptr(self.z1_all[t - 1] if mlp else None),
+                         N.ptr(W1m), N.ptr(W2m), N.ptr(self.A), N.ptr(self.Whh), N.ptr(self.Wp),
+                         N.ptr(dh_prev), N.ptr(dpool), N.ptr(dc_prev), N.ptr(dr_in), None,
+                         N.ptr(None if tail else self.dG_all[t]), N.ptr(self.dz2_all[t - 1] if mlp else None),
+                         N.ptr(self.dz1_all[t - 1] if mlp else None), N.ptr(None if tail else self.drt_all[t]))
+        N.check(_lib().sgg_dec_step_bwd(ctypes.byref(a), N.stream_ptr()), "sgg_dec_step_bwd")
+        return dh_prev, dpool, dc_prev, dr_in
+
+    def weight_grads(self, need):
+        """Every weight gradient from the stacks, in weights() order; `need`:
+        needs_input_grad of those inputs."""
+        T, B, H = self.T, self.B, self.H
+        R = T * B
+        out = [None] * len(need)
+        if not any(need):
+            return out
+        dG = self.dG_all.view(R, 4 * H)
+        W_ih, _Whh, _bi, _bh, We, be = self.lstm_w
+        if any(need[:6]):
+            dW_hh, dbias = xtw(self.hmix_all.view(R, H), dG, colsum=True, trans_c=True)
+            dA = xtw(self.rbuf[:T].reshape(R, 2), dG, trans_c=True)
+            db_hh = torch.empty_like(dbias)
+            dW_ih, dWe, dbe = fold_bwd(W_ih, We, be, dA, dbias, dbias_copy=db_hh)
+            out[:6] = [dW_ih, dW_hh, dbias, db_hh, dWe, dbe]
+        if any(need[6:8]):
+            dWp, dbp = xtw(self.h_all.view(R, H), self.drt_all.view(R, 2), colsum=True, trans_c=True)
+            out[6:8] = [dWp, dbp]
+        if self.fuse_mlp and any(need[8:12]):
+            # mlp application m ran for m < T - 1, and m = T - 1 with the tail
+            Tm = T if self.tail_ran else T - 1
+            Rm, D, bn = Tm * B, self.D, self.bn
+            dW1 = torch.empty(D, H + bn, device=dG.device, dtype=torch.float32)
+            if Rm == 0:
+                out[8:12] = [dW1.zero_(), dW1.new_zeros(D), dW1.new_zeros(H, D), dW1.new_zeros(H)]
+                return out
+            dz1 = self.dz1_all.view(R, D)[:Rm]
+            dW2, db2 = xtw(self.z1_all.view(R, D)[:Rm], self.dz2_all.view(R, H)[:Rm], colsum=True, trans_c=True)
+            _, db1 = xtw(self.h_all.view(R, H)[:Rm], dz1, colsum=True, trans_c=True, out=dW1[:, :H])
+            xtw(torch.cat(self.pools[:Tm], 0), dz1, trans_c=True, out=dW1[:, H:])
+            out[8:12] = [dW1, db1, dW2, db2]
+        return out
+
+
+class _DecStep(torch.autograd.Function):
+    """Step t of a DecRollout (t = T: the tail).  Inputs: the rollout, t, the
+    step's row inputs and -- at t = 0 only -- the rollout's weights."""
+
+    @staticmethod
+    def forward(ctx, ro, t, h_prev, pool_prev, c_prev, r_in, pos_prev, *weights):
+        ctx.ro, ctx.t = ro, t
+        ctx.mlp = ro.fuse_mlp and pool_prev is not None
+        h_prev = _rows(h_prev, "h_prev")
+        pool_prev = _rows(pool_prev, "pool_prev") if pool_prev is not None else None
+        if t == 0:
+            ro.rbuf[0].copy_(r_in)      # the stack of step inputs starts with the caller's
+            r_in = ro.rbuf[0]
+        if t < ro.T:
+            r_in, pos_prev = r_in.contiguous(), pos_prev.contiguous()
+            c_prev = c_prev.contiguous() if c_prev is not None else None
+        if t >= 1:
+            ro.pools[t - 1] = pool_prev
+        ctx.c_prev = c_prev
+        ctx.set_materialize_grads(False)
+        h, c, rel, pos, U = ro.fwd(t, h_prev, pool_prev, c_prev, r_in, pos_prev)
+        if t == ro.T:
+            return h
+        if U is not None:
+            ctx.mark_non_differentiable(U)
+        return h, c, rel, pos, U
+
+    @staticmethod
+    def backward(ctx, dh, dc=None, drel=None, dpos=None, _dU=None):
+        ro, t = ctx.ro, ctx.t
+        cont = lambda g: g.contiguous() if g is not None else None
+        dh, dc, drel, dpos = cont(dh), cont(dc), cont(drel), cont(dpos)
+        nw = len(ctx.needs_input_grad) - 7
+        if t == ro.T and dh is None:
+            return (None,) * (7 + nw)
+        dh_prev, dpool, dc_prev, dr_in = ro.bwd(t, ctx.mlp, ctx.c_prev, dh, dc, drel, dpos)
+        if ctx.c_prev is None:
+            dc_prev = None
+        wg = ro.weight_grads(ctx.needs_input_grad[7:]) if nw else []
+        return (None, None, dh_prev, dpool, dc_prev, dr_in, dpos) + tuple(wg)
+
+
+def dec_rollout(T, B, lstm, emb, proj, mlp, u, fuse_mlp, tensors, dev):
+    """-> a DecRollout for T steps of B peds; `tensors`: the rollout's row
+    inputs (h0, r0, ...), which decide with the weights whether states are saved."""
+    ro_w = [lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, emb.weight, emb.bias,
+            proj.weight, proj.bias] + [p for p in mlp.parameters()] + [u[0], u[1]]
+    save = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in list(tensors) + ro_w)
+    return DecRollout(T, B, lstm, emb, proj, mlp, u, fuse_mlp, save, dev)
+
+
+def dec_step(ro, t, h_prev, pool_prev, c_prev, r_in, pos_prev):
+    """Step t of the rollout -> (h, c, rel, pos, U); t = ro.T: the tail -> h."""
+    ws = ro.weights() if t == 0 else []
+    return _DecStep.apply(ro, t, h_prev, pool_prev, c_prev, r_in, pos_prev, *ws)
+
+
+class _RelStack(torch.autograd.Function):
+    """The rollout's (T, B, 2) output: the steps wrote their rel into one
+    buffer, so the stack is that buffer (no copy); the backward hands each
+    step its slice."""
+
+    @staticmethod
+    def forward(ctx, ro, *rels):
+        ctx.T = len(rels)
+        return ro.rbuf[1:]
+
+    @staticmethod
+    def backward(ctx, dout):
+        return (None,) + tuple(dout[t] for t in range(ctx.T))
+
+
+def dec_rel_stack(ro, rels):
+    return _RelStack.apply(ro, *rels)

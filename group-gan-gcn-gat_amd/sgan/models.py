@@ -168,6 +168,11 @@ class Decoder(nn.Module):
                                      proj=self.hidden2pos, decoder=True, T=self.seq_len)
             return rel, h.unsqueeze(0)
         B = last_pos.size(0)
+        step = self.step_ok() if K.dec_step_enabled() else 0
+        if step:
+            return self._forward_steps(last_pos, last_pos_rel, state_tuple, seq_start_end, scenes, step == 3)
+        if state_tuple[1] is None:   # c0 = 0 (the step kernels take NULL; nn.LSTM needs the tensor)
+            state_tuple = (state_tuple[0], torch.zeros_like(state_tuple[0]))
         x = K.linear(last_pos_rel, self.spatial_embedding).view(1, B, self.embedding_dim)
         outs = []
         for _ in range(self.seq_len):
@@ -176,13 +181,59 @@ class Decoder(nn.Module):
             curr = rel + last_pos
             if self.pool_every_timestep:
                 h = state_tuple[0]
-                pool_h = self.pool_net(h, seq_start_end, curr, scenes=scenes)
+                # (the positions are predictions here: the pooling returns their gradient too)
+                pool_h = self.pool_net(h, seq_start_end, curr, scenes=scenes, pos_grad=True)
                 h = run_mlp(self.mlp, torch.cat([h.view(-1, self.h_dim), pool_h], dim=1))
                 state_tuple = (h.unsqueeze(0), state_tuple[1])
             x = K.linear(rel, self.spatial_embedding).view(1, B, self.embedding_dim)
             outs.append(rel.view(B, -1))
             last_pos = curr
         return torch.stack(outs, dim=0), state_tuple[0]
+
+    def step_ok(self):
+        """Per-step pooling on the step kernels (sgg_dec_step_*): 0 = not for
+        this decoder, 1 = with decoder.mlp on its own Linear launches, 3 = the
+        whole step in one launch."""
+        mods = list(self.mlp) if self.pool_every_timestep else []
+        plain = (len(mods) == 4 and isinstance(mods[0], nn.Linear) and isinstance(mods[1], nn.ReLU)
+                 and isinstance(mods[2], nn.Linear) and isinstance(mods[3], nn.ReLU))
+        if not (plain and self.decoder.num_layers == 1 and isinstance(getattr(self, "pool_net", None), PoolHiddenNet)
+                and self.pool_net.fused_ok()):
+            return 0
+        return K.dec_step_ok(self.h_dim, self.pool_net.bottleneck_dim, mods[0].out_features)
+
+    def _forward_steps(self, last_pos, last_pos_rel, state_tuple, seq_start_end, scenes, fuse_mlp):
+        """models.py:157-175 as one sgg_dec_step_fwd launch per step between
+        the pooling launches: decoder.mlp of the previous pooling, the LSTM
+        cell, hidden2pos, the new position and the pooling net's first layer
+        U.  The returned state (:178) is the same kernel with its cell part
+        off, skipped where nobody reads it (K.final_state_unused)."""
+        T, H, pool = self.seq_len, self.h_dim, self.pool_net
+        sc = _scenes(seq_start_end, last_pos.device, scenes)
+        K.pool_is_wide(sc)   # a scene above the pooling bound: ValueError before any launch
+        h0, c0 = state_tuple
+        h = h0.reshape(-1, H)
+        c = c0.reshape(-1, H) if c0 is not None else None
+        B = h.size(0)
+        K.prefold([K.lstm_fold_spec(self.decoder, self.spatial_embedding), K.pool_fold_spec(pool)])
+        ro = K.dec_rollout(T, B, self.decoder, self.spatial_embedding, self.hidden2pos, self.mlp,
+                           K.pool_u_spec(pool), fuse_mlp, (h, c, last_pos_rel, last_pos), h.device)
+        l1, l2, emb = pool.mlp_pre_pool[0], pool.mlp_pre_pool[2], pool.spatial_embedding
+        rel, pos, pool_h, rels = last_pos_rel, last_pos, None, []
+        for t in range(T):
+            if pool_h is not None and not fuse_mlp:
+                h, pool_h = run_mlp(self.mlp, torch.cat([h, pool_h], dim=1)), None
+            h, c, rel, pos, U = K.dec_step(ro, t, h, pool_h, c, rel, pos)
+            rels.append(rel)
+            pool_h = K.social_pool_pos(h, pos, l1.weight, emb.weight, emb.bias, l1.bias, l2.weight, l2.bias, sc, U=U)
+        out = K.dec_rel_stack(ro, rels)   # (T, B, 2): the steps wrote it in place
+        if K._NO_FINAL[0]:
+            return out, None
+        if fuse_mlp:
+            h = K.dec_step(ro, T, h, pool_h, None, None, None)
+        else:
+            h = run_mlp(self.mlp, torch.cat([h, pool_h], dim=1))
+        return out, h.unsqueeze(0)
 
 
 # ---------------------------------------------------------------------------
@@ -209,15 +260,20 @@ class PoolHiddenNet(nn.Module):
     def fused_ok(self):
         return not (self.batch_norm or self.activation != "relu" or self.dropout > 0)
 
-    def forward(self, h_states, seq_start_end, end_pos, scenes=None, link=None, U=None, dh_in_lstm=False):
+    def forward(self, h_states, seq_start_end, end_pos, scenes=None, link=None, U=None, dh_in_lstm=False,
+                pos_grad=False):
         """U (optional): h W1[:, E:]^T + c already computed by the encoder
-        kernel's epilogue (K.pool_u_spec)."""
+        kernel's epilogue (K.pool_u_spec).  pos_grad: end_pos is a prediction
+        (the per-step rollout), so the backward returns its gradient too."""
         if not self.fused_ok():
             raise NotImplementedError("the fused pooling kernel implements the reference configs "
                                       "(batch_norm=0, relu, dropout=0)")
         sc = _scenes(seq_start_end, end_pos.device, scenes)
         l1, l2 = self.mlp_pre_pool[0], self.mlp_pre_pool[2]
         emb = self.spatial_embedding
+        if pos_grad:
+            return K.social_pool_pos(h_states.reshape(-1, self.h_dim), end_pos, l1.weight, emb.weight, emb.bias,
+                                     l1.bias, l2.weight, l2.bias, sc, U=U)
         return K.social_pool(h_states.reshape(-1, self.h_dim), end_pos, l1.weight, emb.weight, emb.bias, l1.bias,
                              l2.weight, l2.bias, sc, link=link, U=U, dh_in_lstm=dh_in_lstm)
 
@@ -768,6 +824,10 @@ class TrajectoryGenerator(nn.Module):
             specs.append(K.pool_fold_spec(self.pool_net))
         if not self.pool_every_timestep and self.num_layers == 1:
             specs.append(K.lstm_fold_spec(self.decoder.decoder, self.decoder.spatial_embedding))
+        elif self.pool_every_timestep and K.dec_step_enabled() and self.decoder.step_ok():
+            # the step kernels' folded input embedding and the decoder's own pooling net
+            specs.append(K.lstm_fold_spec(self.decoder.decoder, self.decoder.spatial_embedding))
+            specs.append(K.pool_fold_spec(self.decoder.pool_net))
         return specs
 
     def context(self, obs_traj, obs_traj_rel, seq_start_end, obs_traj_g, *, scenes=None):
@@ -929,18 +989,23 @@ class TrajectoryGenerator(nn.Module):
             user_noise = torch.cat(parts, 0)
         last_pos, last_rel = obs_traj[-1], obs_traj_rel[-1]
         if copies > 1:
-            if self.pool_every_timestep:
-                raise NotImplementedError("decode(copies>1) with per-step pooling: run forward() per sample")
+            # (per-step pooling too: the copies are scenes of their own in the replicated index)
             sc = sc.repeat(copies)
             noise_input = noise_input.repeat(copies, 1)
             last_pos, last_rel = last_pos.repeat(copies, 1), last_rel.repeat(copies, 1)
             seq_start_end = None
         decoder_h = self.add_noise(noise_input, seq_start_end, user_noise=user_noise, scenes=sc).unsqueeze(0)
-        # c0 = 0 (models.py:912): the fused decoder takes a NULL initial cell
-        # state as zeros; the per-step fallback needs the tensor
-        decoder_c = (torch.zeros(self.num_layers, sc.B, self.decoder_h_dim, device=obs_traj.device)
-                     if self.pool_every_timestep else None)
-        out, _ = self.decoder(last_pos, last_rel, (decoder_h, decoder_c), seq_start_end, scenes=sc)
+        # c0 = 0 (models.py:912): the fused decoder and the step kernels take
+        # a NULL initial cell state as zeros; the per-op loop makes the tensor
+        if self.pool_every_timestep and self.num_layers != 1:
+            decoder_c = torch.zeros(self.num_layers, sc.B, self.decoder_h_dim, device=obs_traj.device)
+        else:
+            decoder_c = None
+        if not self.pool_every_timestep:
+            out, _ = self.decoder(last_pos, last_rel, (decoder_h, decoder_c), seq_start_end, scenes=sc)
+            return out
+        with K.final_state_unused():   # (the decoder state is discarded, models.py:925: no tail launch)
+            out, _ = self.decoder(last_pos, last_rel, (decoder_h, decoder_c), seq_start_end, scenes=sc)
         return out
 
 

@@ -1015,6 +1015,11 @@ class BucketedGraphTrainer:
     def __init__(self, trainer, ddset, batch_size=64, pad_scenes=32, gran=256, np_caps=(48, 64), pool_cap=None):
         if trainer.dp.on and trainer.dp.world > 1:
             raise NotImplementedError("BucketedGraphTrainer: one rank (the padded batches are not sharded)")
+        if getattr(getattr(trainer, "G", None), "pool_every_timestep", False):
+            # the per-step loop pools on exact scene indices (sgan.scene.PaddedScenes' fixed-capacity
+            # pooling plan is not threaded through it): GraphedTrainer on fixed-size batches, or eager steps
+            raise NotImplementedError("BucketedGraphTrainer: a generator with pool_every_timestep=1 is not "
+                                      "supported on padded batches (use GanTrainer / GraphedTrainer)")
         self.t, self.dd = trainer, ddset
         if pad_scenes < 1:
             # a full batch (S == batch_size) still needs one padding scene to

@@ -1260,6 +1260,87 @@ int sgg_val_metrics(const float* pred_rel, const float* gt, const float* gt_rel,
                     const float* mask, int ld, const float* non_linear, const float* scores, float y_real, int T,
                     int B, double* acc, float* work, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Row-local decoder step of the per-step pooling rollout (Decoder.forward
+ * models.py:157-175 with pool_every_timestep = 1): what the reference does
+ * between two poolings, one launch per step and direction.  The pooling is
+ * an all-to-all seam over a scene's peds and stays its own launch
+ * (sgg_pool_fwd / _wide with this step's U); everything here is per ped:
+ *   mlp  (mlp != 0; steps t >= 1 and the tail):
+ *        z1    = relu(W1m [h_prev | pool_prev] + b1m)      (decoder.mlp, :165-166)
+ *        h_mix = relu(W2m z1 + b2m);        mlp = 0: h_mix = h_prev
+ *   cell (cell != 0):
+ *        gates = A r_in + W_hh h_mix + bias  (A, bias: the folded input embedding, as sgg_lstm_fwd)
+ *        i, f, o = sigmoid, g = tanh;  c = f c_prev + i g;  h = o tanh(c)   (c_prev NULL = 0)
+ *        rel = Wp h + bp (hidden2pos, :159);  pos = pos_prev + rel (:160)
+ *        U   = h Wu^T + cu (U != NULL): the pooling net's first layer on h, NU = 512
+ *   cell = 0 (the tail, :178's returned state): h = h_mix and nothing else is written.
+ * h_prev, h, c, h_mix: B x H; pool_prev: B x bn; r_in, pos_prev, rel, pos: B x 2;
+ * W1m: mlp_dim x (H + bn), W2m: H x mlp_dim, Whh: 4H x H, Wp: 2 x H (nn.Linear
+ * layouts); A: 4H x 2; Wu: NU x H at row stride ldwu; z1: B x mlp_dim; act: B x 4H
+ * (gate activations i | f | g | o).  act, h_mix and z1 are the saved state the
+ * backward reads (each may be NULL in a forward nobody differentiates);
+ * sgg_dec_step_saved_floats(B, H, mlp_dim) = the floats of the three together
+ * (B (5H + mlp_dim), rounded up to 4), caller-owned like every buffer.
+ * fp32 on v_mfma_f32_16x16x4_f32, 16 peds per workgroup, in either precision
+ * of the node transforms.
+ * sgg_dec_step_ok(H, bn, mlp_dim, NU) (host function, no GPU call): 0 where
+ * there is no instantiation -- H must be 16, 32, 48 or 64 and NU 0 or 512;
+ * 3 where the whole step is built: in addition 1 <= bn, H + bn <= 256 and
+ * 1 <= mlp_dim <= 256; 1 where only the mlp is out of those bounds (the caller
+ * runs decoder.mlp as two sgg_xw launches and the step with mlp = 0).
+ *
+ * Backward.  Given dh (the total gradient of h), dc, drel, dpos (each may be
+ * NULL = 0; the tail takes dh only):
+ *   drel_tot = drel + dpos;  dpos_prev = dpos;  dh += Wp^T drel_tot
+ *   cell backward -> dG (gates, pre-activation), dc_prev = dc_tot f
+ *   dr_in = dG A;  dh_mix = dG W_hh
+ *   mlp:  dz2 = dh_mix [h_mix > 0];  dz1 = (dz2 W2m) [z1 > 0];
+ *         [dh_prev | dpool_prev] = dz1 W1m;        mlp = 0: dh_prev = dh_mix
+ * c is the forward's output c, c_prev its input (NULL = 0).  dG (B x 4H), dz2
+ * (B x H), dz1 (B x mlp_dim) and drel_tot (B x 2) are the operands of the
+ * weight gradients, which the caller forms afterwards from the steps' slices
+ * stacked over the rollout (sgg_xtw with column sums, sgg_fold_bwd): dW_hh =
+ * dG^T h_mix, dbias = colsum dG, dA = dG^T r_in, dWp = drel_tot^T h, dbp =
+ * colsum drel_tot, dW2m = dz2^T z1, db2m = colsum dz2, dW1m = dz1^T [h_prev |
+ * pool_prev], db1m = colsum dz1.  dpos_prev may be NULL.  No atomics: the
+ * same input gives the same bits.
+ * Both launches are asynchronous on `stream`, hipGraph-capturable and never
+ * allocate.  SGG_E_ARG (nothing launched) for a shape sgg_dec_step_ok does not
+ * take or a missing operand; B = 0 launches nothing.
+ */
+typedef struct SggDecStep {
+  int B, H, bn, mlp_dim, NU, mlp, cell, ldwu;
+  const float *h_prev, *pool_prev, *c_prev, *r_in, *pos_prev;
+  const float *W1m, *b1m, *W2m, *b2m, *A, *Whh, *bias, *Wp, *bp, *Wu, *cu;
+  float *h, *c, *rel, *pos, *U;
+  float *act, *h_mix, *z1;
+} SggDecStep;
+typedef struct SggDecStepBwd {
+  int B, H, bn, mlp_dim, mlp, cell;
+  const float *dh, *dc, *drel, *dpos;
+  const float *act, *c, *c_prev, *h_mix, *z1;
+  const float *W1m, *W2m, *A, *Whh, *Wp;
+  float *dh_prev, *dpool_prev, *dc_prev, *dr_in, *dpos_prev;
+  float *dG, *dz2, *dz1, *drel_tot;
+} SggDecStepBwd;
+int sgg_dec_step_ok(int H, int bn, int mlp_dim, int NU);
+long long sgg_dec_step_saved_floats(int B, int H, int mlp_dim);
+int sgg_dec_step_fwd(const SggDecStep* a, void* stream);
+int sgg_dec_step_bwd(const SggDecStepBwd* a, void* stream);
+
+/* The pooling's gradient of the positions, which sgg_pool_bwd leaves out
+ * (its callers pool at observed positions).  In the per-step rollout the
+ * positions are predictions (models.py:160, :164), and
+ *   dpos[r] = sum_{(i, c): argmax[i, c] = r} q(i, c) - sum_c q(r, c),
+ *   q(i, c) = g(i, c) sum_k W2[c, k] [hidden(i, j*, k) > 0] A[k, :],  j* = argmax[i, c],
+ * g = dout where out > 0, hidden as in sgg_pool_fwd; the first sum runs over
+ * r's scene in ascending (i, c).  Operands as sgg_pool_bwd's; dpos: B x 2,
+ * every row written.  One wave per ped, any scene size, no atomics. */
+int sgg_pool_dpos(const float* U, const float* pos, const float* A, const float* W2, const float* out,
+                  const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
+                  float* dpos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
