@@ -18,8 +18,10 @@
 //    states its forward wrote), and every forward the rollout does not claim;
 //  - batch-MFMA rollout (lstm_mfma.hip): forwards without saved states where
 //    lstm_fwd_mfma_ok (H = 32, B >= kLstmMfmaMinPeds), unless SGG_LSTM_NO_MFMA.
-// An H that is not built is refused here, before any launch: the H switches
-// of lstm_mw.hip have no error arm.
+//  - generic kernels (lstm_gen.hip): every other 1 <= H <= 128, plain forms only
+//    (sgg_lstm_fwd / sgg_lstm_bwd); the fused forms below stay four-wave only.
+// H <= 0 and H > 128 are refused here, before any launch: the H switches of
+// lstm_mw.hip have no error arm.
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,15 +31,28 @@ using namespace sgg;
 
 extern "C" long long sgg_lstm_state_floats(int T, int B, int H, int which) {
   if (T < 1 || B < 0 || (which != 0 && which != 1)) return -1;
+  if (lstm_gen_ok(H)) return lstm_gen_state_floats(T, B, H, which);
+  if (!lstm_mw_ok(H)) return -1;
   return lstm_mw_state_floats(T, B, H, which);
+}
+
+extern "C" long long sgg_lstm_dg_floats(int T, int B, int H) {
+  if (T < 1 || B < 0 || !(lstm_gen_ok(H) || lstm_mw_ok(H))) return -1;
+  return lstm_gen_ok(H) ? (long long)T * B * 4 * H : 0;
 }
 
 extern "C" const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save, int bwd) {
   // mirrors the dispatch of sgg_lstm_fwd / sgg_lstm_bwd below (save = act_all
   // != NULL for the forward, = weight gradients in the kernel for the backward)
   static char buf[96];
-  if (!lstm_mw_ok(H) || B <= 0) return "";
   const char* tf[2] = {"false", "true"};
+  if (lstm_gen_ok(H) && B > 0) {   // the generic family: the plain forward and backward only
+    if (bwd > 1) return "";
+    if (bwd) snprintf(buf, sizeof buf, "sgg::lstm_gen_bwd_kernel<%d, %s>", lstm_gen_tiles(H), tf[decoder != 0]);
+    else snprintf(buf, sizeof buf, "sgg::lstm_gen_fwd_kernel<%d, %s, %s>", lstm_gen_tiles(H), tf[decoder != 0], tf[save != 0]);
+    return buf;
+  }
+  if (!lstm_mw_ok(H) || B <= 0) return "";
   if (bwd == 3 || bwd == 4) {   // given a pooled-gradient source (sgg_lstm_bwd_pooldh)
     if (decoder || !lstm_mw_bwd_pdh_ok(H) || (bwd == 4 && (!save || !lstm_mw_bwd_nodx_ok(H)))) return "";
     if (bwd == 4) snprintf(buf, sizeof buf, "sgg::lstm_mw_bwd_nodx_pdh_kernel<%d>", H);
@@ -244,8 +259,8 @@ extern "C" int sgg_lstm_bwd_pooldh(const float* A, const float* Whh, const float
 }
 
 extern "C" int sgg_lstm_wpart_rows(int H, int B) {
-  if (B < 0) return -1;
-  return lstm_mw_wpart_rows(H, B);
+  if (B < 0 || !(lstm_gen_ok(H) || lstm_mw_ok(H))) return -1;
+  return lstm_mw_wpart_rows(H, B);   // (one row per 16 peds in either family; the generic one writes dG, no slab)
 }
 
 extern "C" int sgg_lstm_fwd(const float* rel, const float* A, const float* Whh, const float* bias, const float* h0,
@@ -255,8 +270,10 @@ extern "C" int sgg_lstm_fwd(const float* rel, const float* A, const float* Whh, 
   SGG_CHECK_ARG(!decoder || (Wp && bp && rel_out), "sgg_lstm_fwd: decoder needs Wp, bp, rel_out");
   SGG_CHECK_ARG(T >= 1 && B >= 0, "sgg_lstm_fwd: bad sizes T=%d B=%d", T, B);
   if (B == 0) return 0;
-  SGG_CHECK_ARG(lstm_mw_ok(H), "sgg_lstm_fwd: hidden size %d not built (16/32/48/64)", H);
+  SGG_CHECK_ARG(lstm_mw_ok(H) || lstm_gen_ok(H), "sgg_lstm_fwd: hidden size %d (1 .. 128)", H);
   hipStream_t st = (hipStream_t)stream;
+  if (lstm_gen_ok(H))
+    return lstm_gen_fwd(rel, A, Whh, bias, h0, c0, Wp, bp, T, B, H, decoder, h_all, c_all, act_all, rel_out, st);
   // the MFMA rollout only without saved states (inference / no-grad samples):
   // saved states are the four-wave family's, read back by its backward
   if (!act_all && lstm_fwd_mfma_ok(H, B) && !getenv("SGG_LSTM_NO_MFMA"))
@@ -341,10 +358,13 @@ extern "C" int sgg_lstm_bwd(const float* A, const float* Whh, const float* Wp, c
   SGG_CHECK_ARG(!decoder || (Wp && dout && drel_tot), "sgg_lstm_bwd: decoder needs Wp, dout, drel_tot");
   SGG_CHECK_ARG(T >= 1 && B >= 0, "sgg_lstm_bwd: bad sizes");
   if (B == 0) return 0;
-  SGG_CHECK_ARG(lstm_mw_ok(H), "sgg_lstm_bwd: hidden size %d not built (16/32/48/64)", H);
+  SGG_CHECK_ARG(lstm_mw_ok(H) || lstm_gen_ok(H), "sgg_lstm_bwd: hidden size %d (1 .. 128)", H);
+  if (lstm_gen_ok(H))   // the recurrence only: the gate gradients go to dG, no slab is written (sgg.h)
+    return lstm_gen_bwd(A, Whh, Wp, c_all, act_all, dh_last, dout, T, B, H, decoder, dG, dh0, drel_in, drel_tot,
+                        (hipStream_t)stream);
   SGG_CHECK_ARG(!wpart || (h_all && rel && (!decoder || rel_out)),
                 "sgg_lstm_bwd: weight gradients need h_all, rel (and rel_out for the decoder)");
-  (void)dG;   // kept in the signature (sgg.h): ignored
+  (void)dG;   // the four-wave family forms the weight gradients in the kernel: ignored
   return lstm_mw_bwd(A, Whh, Wp, h_all, c_all, act_all, rel, rel_out, dh_last, dout, T, B, H, decoder, dh0, drel_in,
                      drel_tot, wpart, (hipStream_t)stream);
 }

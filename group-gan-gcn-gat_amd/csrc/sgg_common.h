@@ -147,6 +147,26 @@ __attribute__((visibility("hidden"))) int lstm_mw_fwd_dec_seg(const float* A, co
 __attribute__((visibility("hidden"))) int lstm_mw_fwd_seg3(const MwSeg& a, int Ha, const MwSeg& b, int Hb,
                                                            const MwSeg& c, int Hc, hipStream_t st);
 
+// lstm_gen.hip: the generic LSTM sequence kernels, every 1 <= H <= 128 the
+// four-wave family is not built for (lstm_gen_ok): HT = ceil(H / 16) waves per
+// 16 peds, wave w owning hidden units [16 w, 16 w + 16); saved states in its
+// own tile-native layout; the backward runs the recurrence only and stacks
+// the gate gradients in dG (T x B x 4H, may be NULL) for the caller's
+// sgg_xtw products; internal
+__attribute__((visibility("hidden"))) bool lstm_gen_ok(int H);
+__attribute__((visibility("hidden"))) int lstm_gen_tiles(int H);
+__attribute__((visibility("hidden"))) long long lstm_gen_state_floats(int T, int B, int H, int which);
+__attribute__((visibility("hidden"))) int lstm_gen_fwd(const float* rel, const float* A, const float* Whh,
+                                                       const float* bias, const float* h0, const float* c0,
+                                                       const float* Wp, const float* bp, int T, int B, int H,
+                                                       int decoder, float* h_all, float* c_all, float* act_all,
+                                                       float* rel_out, hipStream_t st);
+__attribute__((visibility("hidden"))) int lstm_gen_bwd(const float* A, const float* Whh, const float* Wp,
+                                                       const float* c_all, const float* act_all,
+                                                       const float* dh_last, const float* dout, int T, int B, int H,
+                                                       int decoder, float* dG, float* dh0, float* drel_in,
+                                                       float* drel_tot, hipStream_t st);
+
 // fold.hip: the fold backwards of one sgg_grad_finish in one launch (a
 // workgroup each; dA_src / db_src point at the summed (dA, dbias)); internal
 __attribute__((visibility("hidden"))) void fold_bwd_multi(const SggFoldBwd* folds, int n, hipStream_t st);

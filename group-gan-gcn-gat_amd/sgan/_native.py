@@ -248,6 +248,7 @@ SIGNATURES = {
     "sgg_fold_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "sgg_lstm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sgg_lstm_state_floats": (ctypes.c_longlong, [_i, _i, _i, _i]),
+    "sgg_lstm_dg_floats": (ctypes.c_longlong, [_i, _i, _i]),
     "sgg_lstm_wpart_rows": (_i, [_i, _i]),
     "sgg_lstm_kernel_name": (ctypes.c_char_p, [_i, _i, _i, _i, _i]),
     "sgg_lstm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

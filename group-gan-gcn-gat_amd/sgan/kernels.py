@@ -1209,6 +1209,9 @@ def pool_pair():
     return _scoped(_PRIDER, PoolRider())
 
 
+POOL_MAX_BN = 64   # the pooling kernels' largest bottleneck_dim (pool.hip: 8 / 16 / 32 / 48 / 64)
+
+
 def pool_is_wide(scenes):
     """True when the batch's largest scene is above the LDS-resident pooling
     kernels' bound: the whole batch then goes through sgg_pool_fwd_wide /
@@ -2669,6 +2672,43 @@ def _lstm_finish(wpart, H, W_ih, We, be, first=()):
     return dW_ih, dW_hh, db_ih, db_hh, dWe, dbe
 
 
+def lstm_gen(T, B, H):
+    """The generic LSTM kernel family (lstm_gen.hip) takes this hidden size:
+    every 1 <= H <= 128 the four-wave kernels are not built for.  Its backward
+    stacks the gate gradients (sgg_lstm_dg_floats > 0) instead of writing a
+    slab, and no fused form (projection epilogue, segments, riders, fused
+    decoder start, split / tail / shared / pooled-gradient backward) exists
+    for it: their _ok queries decline and the plain entry points run."""
+    return int(_lib().sgg_lstm_dg_floats(T, B, H)) > 0
+
+
+def _lstm_finish_gen(dG, h_all, r_in, H, W_ih, We, be, dec=None):
+    """_lstm_finish for the generic family: the weight gradients from the
+    stacked gate gradients dG (T x B x 4H), as the per-step decoder forms its
+    own: dW_hh^T = h_prev^T dG with dbias its column sums, dA = dG^T r_in
+    (sgg_xtw_partial), summed and carried through the fold backward by one
+    GradFinish.  dec = (drel_tot, dWp, dbp): also dWp^T = h_next^T drel_tot and
+    dbp.  -> (dW_ih, dW_hh, db_ih, db_hh, dWe, dbe)."""
+    T, B = dG.shape[0], dG.shape[1]
+    R, G4, dev = T * B, 4 * H, dG.device
+    dG2 = dG.view(R, G4)
+    ws_h, sp_h = xtw_partial(h_all[:T].reshape(R, H), dG2, colsum=True)
+    ws_a, sp_a = xtw_partial(dG2, r_in.reshape(R, 2))
+    gf = GradFinish()
+    if dec is not None:
+        drel_tot, dWp, dbp = dec
+        ws_p, sp_p = xtw_partial(h_all[1:].reshape(R, H), drel_tot.view(R, 2), colsum=True)
+        gf.xtw_sums(ws_p, sp_p, H, 2, dWp, trans_c=True, colsum=dbp)
+    dW_hh = torch.empty(G4, H, device=dev, dtype=torch.float32)
+    db_ih = torch.empty(G4, device=dev, dtype=torch.float32)
+    db_hh = torch.empty(G4, device=dev, dtype=torch.float32)
+    gf.xtw_sums(ws_h, sp_h, H, G4, dW_hh, trans_c=True, colsum=db_ih)
+    dW_ih, dWe, dbe = gf.fold(W_ih, We, be, ws_a, sp_a, 2 * G4, 0, ws_h[sp_h * H * G4:], sp_h, G4, 0,
+                              dbias_copy=db_hh)
+    gf.run()
+    return dW_ih, dW_hh, db_ih, db_hh, dWe, dbe
+
+
 class SharedPrefix:
     """The discriminator encoder's observed steps, run once (sgg.h
     SggLstmSeg).  Its input traj_rel = cat(obs_rel, pred) (train.py:404-407,
@@ -3032,7 +3072,9 @@ class _LstmEncoder(torch.autograd.Function):
         dev = rel.device
         need = ctx.needs_input_grad
         wgrad = any(need[1:7])
-        wpart = _lstm_slab(H, B, dev) if wgrad else None
+        gen = lstm_gen(T, B, H)   # (the generic family: stacked gate gradients instead of a slab, no fused form)
+        wpart = _lstm_slab(H, B, dev) if (wgrad and not gen) else None
+        dG = torch.empty(T, B, 4 * H, device=dev, dtype=torch.float32) if (wgrad and gen) else None
         # an input that needs no gradient (data, or a no-grad rollout): the
         # weight-gradient kernel without drel_in, where it is built
         nodx_name = lib.sgg_lstm_kernel_name(H, B, 0, 1, 2).decode() if (wgrad and not need[0]) else ""
@@ -3070,15 +3112,16 @@ class _LstmEncoder(torch.autograd.Function):
             launch = lambda: N.check(lib.sgg_lstm_bwd_shared(
                 N.ptr(A), N.ptr(Whh), N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), N.ptr(dhl), T, B, H,
                 ctx.t_sh, ctx.bsrc, N.ptr(drel_in), N.ptr(wpart), N.stream_ptr()), "sgg_lstm_bwd_shared")
-        elif not wgrad and not has_h0 and 0 < ctx.t_stop < T:
-            # input gradients of steps t_stop .. T-1 only (the rest are not wanted)
+        elif not wgrad and not has_h0 and 0 < ctx.t_stop < T and not gen:
+            # input gradients of steps t_stop .. T-1 only (the rest are not wanted; the generic family has no
+            # such form and computes every row)
             launch = lambda: N.check(lib.sgg_lstm_bwd_tail(
                 N.ptr(A), N.ptr(Whh), N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), N.ptr(dhl), T, B, H,
                 ctx.t_stop, N.ptr(drel_in), N.stream_ptr()), "sgg_lstm_bwd_tail")
         else:
             launch = lambda: N.check(lib.sgg_lstm_bwd(
                 N.ptr(A), N.ptr(Whh), None, N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), None, N.ptr(dhl), None,
-                T, B, H, 0, None, N.ptr(dh0), N.ptr(drel_in), None, N.ptr(wpart), N.stream_ptr()), "sgg_lstm_bwd")
+                T, B, H, 0, N.ptr(dG), N.ptr(dh0), N.ptr(drel_in), None, N.ptr(wpart), N.stream_ptr()), "sgg_lstm_bwd")
         launch()
         if timer.active:
             fl, nb = _lstm_bwd_work(T, B, H, c_all, act, wpart, drel_in is not None, has_h0, False)
@@ -3092,7 +3135,7 @@ class _LstmEncoder(torch.autograd.Function):
                       (T, B, 0, int(wgrad)), fl, nb, launch)
         grads = (None,) * 6
         if wgrad:
-            grads = _lstm_finish(wpart, H, W_ih, We, be)
+            grads = _lstm_finish_gen(dG, h_all, rel, H, W_ih, We, be) if gen else _lstm_finish(wpart, H, W_ih, We, be)
         return (drel_in,) + grads + (dh0, None, None, None, None, None)   # (drel_in None: not wanted, not computed)
 
 
@@ -3158,7 +3201,8 @@ class _LstmDecoder(torch.autograd.Function):
                     N.ctypes.byref(di), N.ptr(A), N.ptr(Whh), N.ptr(bias), N.ptr(Wpc), N.ptr(bp), T, B, H,
                     N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel_out), N.ptr(rel) if save else None,
                     N.ctypes.byref(to) if to is not None else None, N.stream_ptr())
-                if drider is not None and not final and Wpc is not None:
+                # (a hidden size of the generic family has no fused start: nothing to hold or to pair)
+                if drider is not None and not final and Wpc is not None and not lstm_gen(T, B, H):
                     if to is not None and drider.held is None and not drider.done:
                         hold = True   # the discriminator step's decoder (either family): held for the rollout's launch
                     elif ("mfma" in lib.sgg_lstm_kernel_name(H, B, 1, 0, 0).decode()
@@ -3209,7 +3253,9 @@ class _LstmDecoder(torch.autograd.Function):
         dev = rel.device
         need = ctx.needs_input_grad
         wgrad, need_p = any(need[1:7]), need[9] or need[10]
-        wpart = _lstm_slab(H, B, dev, 2 * H + 2) if wgrad else None   # (+ [dWp (2 x H) | dbp (2)])
+        gen = lstm_gen(T, B, H)   # (the generic family: stacked gate gradients, no split form)
+        wpart = _lstm_slab(H, B, dev, 2 * H + 2) if (wgrad and not gen) else None   # (+ [dWp (2 x H) | dbp (2)])
+        dG = torch.empty(T, B, 4 * H, device=dev, dtype=torch.float32) if (wgrad and gen) else None
         drel_in = torch.empty(T, B, 2, device=dev, dtype=torch.float32)
         dh0 = torch.empty(B, H, device=dev, dtype=torch.float32) if has_h0 else None
         drel_tot = torch.empty(T, B, 2, device=dev, dtype=torch.float32)
@@ -3219,7 +3265,7 @@ class _LstmDecoder(torch.autograd.Function):
             ga, gb, bsplit, ph = pend
             if drel_out is None or drel_out.data_ptr() != ph.data_ptr():
                 raise N.NativeError("decoder backward: the split rollout output has another consumer")
-            if wgrad:   # the kernel reads the two blocks in place
+            if wgrad and not gen:   # the kernel reads the two blocks in place
                 split = (ga, gb, bsplit)
             else:
                 drel_out = torch.cat([ga, gb], 1)
@@ -3230,9 +3276,9 @@ class _LstmDecoder(torch.autograd.Function):
                 N.ptr(wpart), N.stream_ptr()), "sgg_lstm_bwd_split")
         else:
             dout = drel_out.contiguous() if drel_out is not None else torch.zeros(T, B, 2, device=dev)
-            launch = lambda: N.check(lib.sgg_lstm_bwd(   # (the two None: dh_last; dG, ignored -- sgg.h)
+            launch = lambda: N.check(lib.sgg_lstm_bwd(   # (the None: dh_last; dG: the generic family's -- sgg.h)
                 N.ptr(A), N.ptr(Whh), N.ptr(Wp), N.ptr(h_all), N.ptr(c_all), N.ptr(act), N.ptr(rel), N.ptr(rel_out),
-                None, N.ptr(dout), T, B, H, 1, None, N.ptr(dh0), N.ptr(drel_in), N.ptr(drel_tot), N.ptr(wpart),
+                None, N.ptr(dout), T, B, H, 1, N.ptr(dG), N.ptr(dh0), N.ptr(drel_in), N.ptr(drel_tot), N.ptr(wpart),
                 N.stream_ptr()), "sgg_lstm_bwd")
         launch()
         if timer.active:
@@ -3244,6 +3290,10 @@ class _LstmDecoder(torch.autograd.Function):
             if need_p:   # accumulated by the kernel into the slab rows' last columns
                 dWp = torch.empty(2, H, device=dev, dtype=torch.float32)
                 dbp = torch.empty(2, device=dev, dtype=torch.float32)
+            if gen:   # r_in(t): the first input, then the step before's prediction
+                r_in = torch.cat([rel.view(1, B, 2), rel_out[:T - 1]], 0)
+                grads = _lstm_finish_gen(dG, h_all, r_in, H, W_ih, We, be, (drel_tot, dWp, dbp) if need_p else None)
+                return (drel_in[0],) + grads + (dh0, None, dWp, dbp, None, None, None)
             P = wpart.shape[1] - 2 * H - 2
             grads = _lstm_finish(wpart, H, W_ih, We, be, ((P, 2 * H, dWp), (P + 2 * H, 2, dbp)) if need_p else ())
         elif need_p:   # a frozen LSTM under a trainable hidden2pos

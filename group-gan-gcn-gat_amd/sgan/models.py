@@ -1036,6 +1036,11 @@ class TrajectoryDiscriminator(nn.Module):
 
     def forward(self, traj, traj_rel, seq_start_end=None, *, scenes=None):
         if self.d_type != "local":
+            if self.pool_net.bottleneck_dim > K.POOL_MAX_BN:   # (bn = h_dim here: refused before any launch)
+                raise K.N.NativeError("TrajectoryDiscriminator(d_type='global', h_dim=%d): the pooling net's "
+                                      "bottleneck_dim is h_dim, and the pooling kernels take bottleneck_dim <= %d "
+                                      "(the LSTM itself takes h_dim <= 128: use d_type='local')"
+                                      % (self.h_dim, K.POOL_MAX_BN))
             scenes = _scenes(seq_start_end, traj.device, scenes)
             K.pool_is_wide(scenes)   # a scene above the pooling bound: ValueError before any launch
         if self.encoder.num_layers == 1:   # encoder + pooling folds in one launch (kernels.prefold)

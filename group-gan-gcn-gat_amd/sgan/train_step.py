@@ -1020,6 +1020,14 @@ class BucketedGraphTrainer:
             # pooling plan is not threaded through it): GraphedTrainer on fixed-size batches, or eager steps
             raise NotImplementedError("BucketedGraphTrainer: a generator with pool_every_timestep=1 is not "
                                       "supported on padded batches (use GanTrainer / GraphedTrainer)")
+        for net in (getattr(trainer, "G", None), getattr(trainer, "D", None)):
+            for name, m in (net.named_modules() if net is not None else ()):
+                if isinstance(m, torch.nn.LSTM) and K.lstm_gen(1, 1, m.hidden_size):
+                    # the padded-batch contract (tests/test_gpu_padded.py) is pinned kernel by kernel for the
+                    # four-wave LSTM sizes only: refused here, before any launch
+                    raise NotImplementedError("BucketedGraphTrainer: LSTM %s has hidden size H=%d; padded batches "
+                                              "run on the four-wave LSTM kernels only (H in 16 / 32 / 48 / 64) -- "
+                                              "use GanTrainer / GraphedTrainer" % (name, m.hidden_size))
         self.t, self.dd = trainer, ddset
         if pad_scenes < 1:
             # a full batch (S == batch_size) still needs one padding scene to

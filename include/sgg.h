@@ -648,14 +648,25 @@ int sgg_fold_bwd(const float* W, int ldw, int R, int E, const float* We, const f
  * encoder (decoder = 0): r_t = rel[t] (T x B x 2); h_{-1} = h0, c_{-1} = c0 (NULL = 0).
  * decoder (decoder = 1): r_0 = rel (B x 2), r_t = Wp h_{t-1} + bp (hidden2pos) for
  *   t >= 1; rel_out[t] = Wp h_t + bp (T x B x 2) is the predicted displacement.
- * H in {16, 32, 48, 64}.  h_all: (T+1) x B x H with index 0 the initial state.
+ * 1 <= H <= 128: H in {16, 32, 48, 64} runs on the four-wave kernels, every
+ * other size on the generic family (HT = ceil(H / 16) waves per 16 peds, H a
+ * runtime argument; nothing is read or written past H or B in any buffer
+ * below except the family's own padded saved states).  H <= 0 and H > 128 are
+ * SGG_E_ARG (the size functions return -1).  h_all: (T+1) x B x H with index
+ * 0 the initial state.
  * act_all (gate activations) and c_all (cells) are the saved states the
- * backward reads, in the tile-native layout of the four-wave kernels (B
- * padded to 16 peds): allocate sgg_lstm_state_floats(T, B, H, 0) floats for
- * act_all and (.., 1) for c_all.  act_all may be NULL (inference: then only
- * h_all[T] is written) and is required by the backward.
+ * backward reads, in the tile-native layout of the family that takes H (B
+ * padded to 16 peds; the generic family also pads H to 16 HT): allocate
+ * sgg_lstm_state_floats(T, B, H, 0) floats for act_all and (.., 1) for c_all,
+ * 16-byte aligned.  act_all may be NULL (inference: then only h_all[T] is
+ * written) and is required by the backward.
  */
 long long sgg_lstm_state_floats(int T, int B, int H, int which);
+/* Floats of the stacked gate-gradient buffer dG (T x B x 4H) that sgg_lstm_bwd
+ * fills for the hidden sizes of the generic family; 0 for the four-wave
+ * sizes, whose backward forms the weight gradients in the kernel; -1 for an
+ * H that no family takes. */
+long long sgg_lstm_dg_floats(int T, int B, int H);
 int sgg_lstm_fwd(const float* rel, const float* A, const float* Whh, const float* bias,
                  const float* h0, const float* c0, const float* Wp, const float* bp, int T, int B, int H,
                  int decoder, float* h_all, float* c_all, float* act_all, float* rel_out,
@@ -756,20 +767,35 @@ int sgg_lstm_fwd_u(const float* rel, const float* A, const float* Whh, const flo
  * sgg_slab_reduce / sgg_grad_finish sum the rows.  wpart = NULL: input
  * gradients only (frozen weights; dWp / dbp of a decoder are then X^T sums
  * of drel_tot and h_all, left to the caller).
- * The dG parameter is ignored and callers pass NULL: it only keeps the
- * argument list, which many ctypes callers spell out, as it is.
+ * dG: ignored for H in {16, 32, 48, 64} (callers pass NULL).  For every other
+ * H (the generic family, sgg_lstm_dg_floats(T, B, H) > 0) the kernel runs the
+ * recurrence only: wpart is not written (it may be NULL, and
+ * sgg_lstm_wpart_rows still counts the launch's workgroups), and dG, when not
+ * NULL, receives the gate gradients dG[t][p][gate H + u] (T x B x 4H, gate
+ * order i, f, g, o).  The caller forms the weight gradients from it in a fixed
+ * order with sgg_xtw_partial / sgg_grad_finish:
+ *   dW_hh = dG^T h_all[0 .. T-1],  dbias = column sums of dG,
+ *   dA = dG^T r_in (r_in(t) = rel[t]; decoder: rel, then rel_out[t-1]),
+ *   decoder: dWp = drel_tot^T h_all[1 .. T], dbp = column sums of drel_tot.
+ * h_all, rel and rel_out are not read by that family's backward.
  * drel_in may be NULL where the input gradient is not wanted (the input is
  * data, or comes from a no-grad rollout), for an encoder (decoder = 0)
  * with wpart and H = 16 / 32 / 48: the kernel then leaves
  * out everything that forms it, and the slab and dh0 are bit-identical to the
- * call with a buffer.  In every other case NULL is SGG_E_ARG (nothing is
- * launched). */
+ * call with a buffer.  In every other case (the generic family included) NULL
+ * is SGG_E_ARG (nothing is launched). */
 int sgg_lstm_wpart_rows(int H, int B);
 /* Name of the kernel sgg_lstm_fwd (bwd = 0; save = act_all != NULL) or
  * sgg_lstm_bwd (bwd = 1; bwd = 2: given drel_in = NULL, "" where that is an
  * argument error) launches for these sizes, as rocprofv3 lists it
  * (bench.py's per-kernel timing).  bwd = 3 / 4: sgg_lstm_bwd_pooldh's kernel
- * in the place of bwd = 1 / 2's ("" where it is not built). */
+ * in the place of bwd = 1 / 2's ("" where it is not built).  The generic
+ * family (H outside {16, 32, 48, 64}) has the plain kernels only:
+ * sgg::lstm_gen_fwd_kernel<HT, decoder, save>, sgg::lstm_gen_bwd_kernel<HT,
+ * decoder> for bwd = 1 (save ignored), "" for bwd >= 2.  Every fused form
+ * below (_fwd_u, _fwd_seg*, _fwd_dec*, _bwd_split, _bwd_tail, _bwd_shared,
+ * _bwd_pooldh) stays four-wave only: SGG_E_ARG, or 0 from its _ok query, for
+ * the generic sizes, and the caller runs the plain entry points. */
 const char* sgg_lstm_kernel_name(int H, int B, int decoder, int save, int bwd);
 /* The decoder backward with
  * the output gradient in two blocks: peds < bsplit from dout (T x bsplit x 2),
