@@ -24,4 +24,9 @@ static inline int device_cus() {
   return ncu;
 }
 
+// the row-chunk planner of the tiled forwards (pool_wide.hip), shared by
+// sgg_pool_plan_wide and sgg_pool_plan_bn; `name` prefixes its error messages
+int pool_plan_rows(const char* name, const int32_t* host_scene_off, int S, int gpw, int target_chunks,
+                   int32_t* chunks, int cap, int* max_rows, int* gpw_out);
+
 }  // namespace sgg

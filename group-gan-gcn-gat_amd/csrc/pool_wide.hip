@@ -8,208 +8,20 @@
 
 #include "sgg_common.h"
 #include "pool_common.h"
+#include "pool_tiled_fwd.h"
 
 namespace sgg {
 
 // ---- forward ------------------------------------------------------------------
-// Work unit = a chunk of whole i-rows [i0, i1) of one scene (sgg_pool_plan_wide),
-// so max_j still completes inside one workgroup (LDS atomics only).  The
-// workgroup walks the scene's j in tiles of <= 64 peds and, inside a tile, its
-// rows x nj pairs (j fastest) in passes of its pair capacity (4 waves x GPW
-// groups x 16 pairs).  A pass is pool_fwd_kernel's chunk body: the 512 hidden
-// units in k-tiles of 64 staged in LDS (the j-tile's U rows, W2^T tile, A
-// tile), k-steps of 4 through v_mfma_f32_16x16x4_f32, one hidden value per lane
-// and group (2 FMA + max), bias then ReLU -- a pair's value does not depend on
-// the tiling, so it is bitwise pool_fwd_kernel's.  The keys (value bits << 32 |
-// ~j, j scene-local) live in LDS across all tiles and passes and are written
-// out once.  The next k-tile -- of this pass, or the first of the next pass /
-// j-tile -- is register-staged while the current one computes.
-constexpr int kWKT = 64;           // hidden units per LDS k-tile
-constexpr int kWKTP = kWKT + 2;    // U tile row stride: (2j + k) mod 32 -> conflict-free b32 reads
-constexpr int kWJT = 64;           // peds per j-tile
-constexpr int kWideWaves = 4;
-
+// pool_tiled_fwd.h: the body shared with the column-tiled family (pool_bn.hip); here every column of the
+// template width, compile-time strides.
 template <int BN, int GPW>
 __global__ void __launch_bounds__(256) pool_fwd_wide_kernel(
     const float* __restrict__ U, const float* __restrict__ pos, const float* __restrict__ A,
     const float* __restrict__ W2 /* BN x 512 */, const float* __restrict__ b2,
     const int32_t* __restrict__ scene_off, const int4* __restrict__ chunks, int nch, float* __restrict__ out,
     int32_t* __restrict__ argmax) {
-  using C = PoolCfg<BN>;
-  constexpr int NT = C::NT, BNP = C::BNP;
-  constexpr int P = 16 * kWideWaves * GPW;   // pairs of one pass
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* Us = reinterpret_cast<float*>(smem);                              // kWJT x kWKTP
-  float* W2s = Us + kWJT * kWKTP;                                          // kWKT x BNP
-  float* As = W2s + kWKT * BNP;                                            // kWKT x 2
-  float2* ps = reinterpret_cast<float2*>(As + 2 * kWKT);                   // scene positions (<= 1024)
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(ps + SGG_POOL_WIDE_MAX_PEDS);  // rows x BN
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c16 = lane & 15, kq = lane >> 4;
-  float bv[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) bv[t] = b2[min(16 * t + c16, BN - 1)];
-
-  // XCD-aware chunk order (pool_fwd_kernel): the grid is a multiple of 8
-  const int gstride = (int)gridDim.x;
-  const int xb = ((int)blockIdx.x & 7) * (gstride >> 3) + ((int)blockIdx.x >> 3);
-  for (int ch = xb; ch < nch; ch += gstride) {
-    const int4 cd = chunks[ch];
-    const int s = cd.x, i0 = cd.y, i1 = cd.z;
-    if (i1 <= i0) continue;
-    const int o = scene_off[s];
-    const int n = scene_off[s + 1] - o;
-    const int rows = i1 - i0;
-    const int ntiles = (n + kWJT - 1) / kWJT;
-
-    for (int q = threadIdx.x; q < n; q += blockDim.x) ps[q] = make_float2(pos[2 * (o + q)], pos[2 * (o + q) + 1]);
-    for (int q = threadIdx.x; q < rows * BN; q += blockDim.x) keys[q] = 0ull;
-
-    constexpr int kUQ = (kWJT * (kWKT / 4) + 255) / 256;   // float4 of U per thread
-    constexpr int kWQ = (kWKT * BNP + 255) / 256;          // W2^T floats per thread
-    float4 ureg[kUQ];
-    float wreg[kWQ];
-    float areg = 0.f;
-    int nj_ld = 0;   // rows of the register-staged U tile
-    auto load_tile = [&](int jb, int nj, int k0) {
-      nj_ld = nj;
-#pragma unroll
-      for (int e = 0; e < kUQ; ++e) {
-        const int q = threadIdx.x + 256 * e;
-        const int r = q / (kWKT / 4), c4 = q - r * (kWKT / 4);
-        if (r < nj) ureg[e] = *reinterpret_cast<const float4*>(U + (size_t)(o + jb + r) * kHidden + k0 + 4 * c4);
-      }
-#pragma unroll
-      for (int e = 0; e < kWQ; ++e) {   // W2 (BN x 512, nn.Linear layout), read transposed
-        const int q = threadIdx.x + 256 * e;
-        const int kk = q / BNP, cc = q - kk * BNP;
-        wreg[e] = (kk < kWKT && cc < BN) ? W2[(size_t)cc * kHidden + k0 + kk] : 0.f;
-      }
-      if (threadIdx.x < 2 * kWKT) areg = A[2 * k0 + threadIdx.x];
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-      for (int e = 0; e < kUQ; ++e) {
-        const int q = threadIdx.x + 256 * e;
-        const int r = q / (kWKT / 4), c4 = q - r * (kWKT / 4);
-        if (r < nj_ld) {
-          float* d = Us + r * kWKTP + 4 * c4;
-          d[0] = ureg[e].x; d[1] = ureg[e].y; d[2] = ureg[e].z; d[3] = ureg[e].w;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < kWQ; ++e) {
-        const int q = threadIdx.x + 256 * e;
-        if (q < kWKT * BNP) W2s[q] = wreg[e];
-      }
-      if (threadIdx.x < 2 * kWKT) As[threadIdx.x] = areg;
-    };
-
-    load_tile(0, min(kWJT, n), 0);
-    __syncthreads();  // ps / keys init visible; the previous chunk's readers done
-    store_tile();
-    __syncthreads();
-    for (int jt = 0; jt < ntiles; ++jt) {
-      const int jb = jt * kWJT;
-      const int nj = min(kWJT, n - jb);
-      const int npairs = rows * nj;
-      const int npass = (npairs + P - 1) / P;
-      for (int pa = 0; pa < npass; ++pa) {
-        // what follows this pass: another pass of the tile, the next tile, or nothing
-        const bool more = pa + 1 < npass || jt + 1 < ntiles;
-        const int jb_n = pa + 1 < npass ? jb : jb + kWJT;
-        const int nj_n = min(kWJT, n - jb_n);
-
-        // per-lane A-row pair of each group (padding pairs -> the tile's first j, r = 0)
-        int uoff[GPW];
-        float rx[GPW], ry[GPW];
-        floatx4 acc[GPW][NT];
-#pragma unroll
-        for (int g = 0; g < GPW; ++g) {
-          const int p = pa * P + (wave * GPW + g) * 16 + c16;
-          int il = 0, jl = 0;
-          if (p < npairs) { il = p / nj; jl = p - il * nj; }
-          uoff[g] = jl * kWKTP + kq;
-          const float2 pj = ps[jb + jl], pi = ps[i0 + il];
-          rx[g] = p < npairs ? pj.x - pi.x : 0.f;
-          ry[g] = p < npairs ? pj.y - pi.y : 0.f;
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = floatx4{0.f, 0.f, 0.f, 0.f};
-        }
-
-        for (int k0 = 0; k0 < kHidden; k0 += kWKT) {
-          const bool last_k = k0 + kWKT >= kHidden;
-          if (!last_k) load_tile(jb, nj, k0 + kWKT);
-          else if (more) load_tile(jb_n, nj_n, 0);
-          float b[NT], u[GPW];
-          float2 a;
-#pragma unroll
-          for (int t = 0; t < NT; ++t) b[t] = W2s[kq * BNP + 16 * t + c16];
-          a = *reinterpret_cast<const float2*>(As + 2 * kq);
-#pragma unroll
-          for (int g = 0; g < GPW; ++g) u[g] = Us[uoff[g]];
-#pragma unroll 2
-          for (int s4 = 0; s4 < kWKT / 4; ++s4) {
-            float h[GPW], bc[NT];
-#pragma unroll
-            for (int g = 0; g < GPW; ++g) h[g] = fmaxf(fmaf(a.y, ry[g], fmaf(a.x, rx[g], u[g])), 0.f);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) bc[t] = b[t];
-            if (s4 + 1 < kWKT / 4) {  // prefetch the next k-step's operands
-              const int kn = 4 * (s4 + 1);
-#pragma unroll
-              for (int t = 0; t < NT; ++t) b[t] = W2s[(kn + kq) * BNP + 16 * t + c16];
-              a = *reinterpret_cast<const float2*>(As + 2 * (kn + kq));
-#pragma unroll
-              for (int g = 0; g < GPW; ++g) u[g] = Us[uoff[g] + kn];
-            }
-#pragma unroll
-            for (int g = 0; g < GPW; ++g)
-#pragma unroll
-              for (int t = 0; t < NT; ++t)
-                acc[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(h[g], bc[t], acc[g][t], 0, 0, 0);
-          }
-          __syncthreads();  // tile consumed
-          if (!last_k || more) {
-            store_tile();
-            __syncthreads();
-          }
-        }
-
-        // epilogue: bias, ReLU, max over j (LDS atomic max on (bits << 32 | ~j))
-#pragma unroll
-        for (int g = 0; g < GPW; ++g) {
-          const int grp = wave * GPW + g;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int p = pa * P + grp * 16 + kq * 4 + r;
-            if (p < npairs) {
-              const int il = p / nj, j = jb + (p - il * nj);
-              const unsigned long long jkey = 0xFFFFFFFFull - (unsigned long long)j;
-#pragma unroll
-              for (int t = 0; t < NT; ++t) {
-                const int cc = 16 * t + c16;
-                if (cc < BN) {
-                  float v = acc[g][t][r] + bv[t];
-                  v = v > 0.f ? v : 0.f;
-                  atomicMax(&keys[il * BN + cc], ((unsigned long long)__float_as_uint(v) << 32) | jkey);
-                }
-              }
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < rows * BN; q += blockDim.x) {
-      const unsigned long long key = keys[q];
-      const size_t oi = (size_t)(o + i0) * BN + q;
-      out[oi] = __uint_as_float((unsigned)(key >> 32));
-      argmax[oi] = o + (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-    }
-    __syncthreads();
-  }
+  pool_fwd_tiled_body<BN, GPW, false>(U, pos, A, W2, b2, scene_off, chunks, nch, out, argmax, 0, BN);
 }
 
 // ---- backward -----------------------------------------------------------------
@@ -344,13 +156,6 @@ __global__ void __launch_bounds__(512) pool_bwd_wide_kernel(
   }
 }
 
-template <int BN>
-static size_t wide_fwd_lds(int max_rows) {
-  using C = PoolCfg<BN>;
-  return sizeof(float) * ((size_t)kWJT * kWKTP + (size_t)kWKT * C::BNP + 2 * kWKT) +
-         sizeof(float2) * SGG_POOL_WIDE_MAX_PEDS + sizeof(unsigned long long) * (size_t)max_rows * BN;
-}
-
 // pair groups per wave: the resident kernel's measured caps
 static int wide_gpw(int bn) { return bn > 16 ? 4 : 2; }
 
@@ -362,7 +167,7 @@ static int launch_fwd_wide(const float* U, const float* pos, const float* A, con
   int grid = (nchunks + 7) & ~7;
   const int cap = 4 * ((device_cus() + 7) & ~7);
   if (grid > cap) grid = cap;
-  hipLaunchKernelGGL((pool_fwd_wide_kernel<BN, GPW>), dim3(grid), dim3(256), wide_fwd_lds<BN>(max_rows), st, U, pos, A,
+  hipLaunchKernelGGL((pool_fwd_wide_kernel<BN, GPW>), dim3(grid), dim3(256), pool_fwd_tiled_lds<BN>(max_rows), st, U, pos, A,
                      W2, b2, off, reinterpret_cast<const int4*>(chunks), nchunks, out, am);
   SGG_RETURN_LAUNCH("sgg_pool_fwd_wide");
 }
@@ -397,24 +202,20 @@ using namespace sgg;
 
 static bool wide_bn_ok(int bn) { return bn == 8 || bn == 16 || bn == 32 || bn == 48 || bn == 64; }
 
-extern "C" int sgg_pool_plan_wide(const int32_t* host_scene_off, int S, int bn, int target_chunks,
-                                  int32_t* chunks, int cap, int* max_rows, int* gpw_out) {
-  // host helper: chunks of whole i-rows, at most rmax rows each -- rmax the
-  // largest of 64, 32, .. gpw that still yields >= target_chunks chunks (64
-  // bounds the keys in LDS; gpw rows x a full 64-ped j-tile fill one pass) --
-  // rows spread evenly over a scene's chunks
-  if (!host_scene_off || !chunks || !max_rows || !gpw_out || S < 0 || cap < 0 || !wide_bn_ok(bn)) {
-    sgg::set_error("sgg_pool_plan_wide: bad argument");
-    return SGG_E_ARG;
-  }
+// host helper of sgg_pool_plan_wide / sgg_pool_plan_bn (arguments checked by
+// the caller): chunks of whole i-rows, at most rmax rows each -- rmax the
+// largest of 64, 32, .. gpw that still yields >= target_chunks chunks (64
+// bounds the keys in LDS; gpw rows x a full 64-ped j-tile fill one pass) --
+// rows spread evenly over a scene's chunks
+int sgg::pool_plan_rows(const char* name, const int32_t* host_scene_off, int S, int gpw, int target_chunks,
+                        int32_t* chunks, int cap, int* max_rows, int* gpw_out) {
   for (int s = 0; s < S; ++s) {
     const int n = host_scene_off[s + 1] - host_scene_off[s];
     if (n < 0 || n > SGG_POOL_WIDE_MAX_PEDS) {
-      sgg::set_error("sgg_pool_plan_wide: scene %d has %d peds, outside [0, %d]", s, n, SGG_POOL_WIDE_MAX_PEDS);
+      sgg::set_error("%s: scene %d has %d peds, outside [0, %d]", name, s, n, SGG_POOL_WIDE_MAX_PEDS);
       return SGG_E_ARG;
     }
   }
-  const int gpw = wide_gpw(bn);
   int rmax = 64;
   for (; rmax > gpw; rmax >>= 1) {
     long nc = 0;
@@ -432,7 +233,7 @@ extern "C" int sgg_pool_plan_wide(const int32_t* host_scene_off, int S, int bn, 
     for (int i0 = 0; i0 < n; i0 += rows) {
       const int i1 = i0 + rows < n ? i0 + rows : n;
       if (nc >= cap) {
-        sgg::set_error("sgg_pool_plan_wide: chunk table capacity %d exceeded", cap);
+        sgg::set_error("%s: chunk table capacity %d exceeded", name, cap);
         return SGG_E_ARG;
       }
       chunks[4 * nc + 0] = s;
@@ -446,6 +247,16 @@ extern "C" int sgg_pool_plan_wide(const int32_t* host_scene_off, int S, int bn, 
   *max_rows = mr;
   *gpw_out = gpw;
   return nc;
+}
+
+extern "C" int sgg_pool_plan_wide(const int32_t* host_scene_off, int S, int bn, int target_chunks,
+                                  int32_t* chunks, int cap, int* max_rows, int* gpw_out) {
+  if (!host_scene_off || !chunks || !max_rows || !gpw_out || S < 0 || cap < 0 || !wide_bn_ok(bn)) {
+    sgg::set_error("sgg_pool_plan_wide: bad argument");
+    return SGG_E_ARG;
+  }
+  return pool_plan_rows("sgg_pool_plan_wide", host_scene_off, S, wide_gpw(bn), target_chunks, chunks, cap, max_rows,
+                        gpw_out);
 }
 
 extern "C" int sgg_pool_fwd_wide(const float* U, const float* pos, const float* A, const float* W2, const float* b2,

@@ -183,6 +183,11 @@ SIGNATURES = {
     "sgg_pool_fwd_wide": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sgg_pool_bwd_wide_grid": (_i, [_i, _i]),
     "sgg_pool_bwd_wide": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "sgg_pool_plan_bn": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
+    "sgg_pool_fwd_bn": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sgg_pool_bwd_bn_grid": (_i, [_i, _i, _i]),
+    "sgg_pool_bwd_bn_ws_floats": (ctypes.c_longlong, [_i, _i, _i, _i]),
+    "sgg_pool_bwd_bn": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "sgg_gat_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _i, _p]),
     "sgg_gat_bwd": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
     "sgg_gat_fwd_ex": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _i, _p]),

@@ -1136,6 +1136,12 @@ def _pool_flops(scenes, bn):
     return float((sz * sz).sum()) * 512.0 * (4 + 2 * bn)
 
 
+def _pool_flops_bn(scenes, bn):
+    import numpy as np
+    sz = np.diff(scenes.host_off).astype(np.float64)
+    return float((sz * sz).sum()) * 512.0 * (4 * ((bn + 63) // 64) + 2 * bn)
+
+
 def _pool_kname(bn, gpw, nchunks, bf16, dev, max_n=None, max_rows=None):
     """The forward kernel the library picks (pool.hip launch_fwd_g / launch_fwd_bf16)."""
     if bf16:
@@ -1210,6 +1216,15 @@ def pool_pair():
 
 
 POOL_MAX_BN = 64   # the pooling kernels' largest bottleneck_dim (pool.hip: 8 / 16 / 32 / 48 / 64)
+POOL_BN_MAX = 1024  # the column-tiled family's (pool_bn.hip, SGG_POOL_BN_MAX): every other width up to it
+
+
+def pool_bn_built(bn):
+    """True for the widths pool.hip / pool_wide.hip are instantiated for; any
+    other width (up to POOL_BN_MAX) runs on the column-tiled family
+    (sgg_pool_fwd_bn / sgg_pool_bwd_bn) at every scene size."""
+    from .scene import POOL_BUILT_BN
+    return bn in POOL_BUILT_BN
 
 
 def pool_is_wide(scenes):
@@ -1249,6 +1264,16 @@ class _Pool(torch.autograd.Function):
         W1 = W1.contiguous()
         W2 = W2.contiguous()
         b2 = b2.contiguous()
+        # a width pool.hip / pool_wide.hip are not built for: the column-tiled family at every scene
+        # size; like a wide launch fp32 in either precision, never paired, no dh handoff.  Its bound
+        # and its plan come before the first launch: a fixed-capacity batch (PaddedScenes) refuses
+        # such a width there, by name
+        fam = not pool_bn_built(bn)
+        if fam and bn > POOL_BN_MAX:
+            raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
+                                "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
+        fam_plan = scenes.pool_plan(bn, family_bn=True) if fam else None
+        tiled = wide or fam    # a tiled launch: neither held nor carried by the paired launch
         A, c = fold_fwd(W1[:, :E], We, be, b1)
         if U is None:
             U = xw_raw(h, W1[:, E:], c, trans_w=True)             # B x 512
@@ -1257,14 +1282,21 @@ class _Pool(torch.autograd.Function):
         out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
         am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
         # the opt-in bf16 precision: the 512 -> bn contraction on bf16 MFMA (its own chunk plan)
-        bf16 = _PRECISION == "bf16" and not wide
-        plan = scenes.pool_plan(bn, wide=True) if wide else scenes.pool_plan(bn, bf16=bf16)
+        bf16 = _PRECISION == "bf16" and not tiled
+        plan = fam_plan if fam else scenes.pool_plan(bn, wide=True) if wide else scenes.pool_plan(bn, bf16=bf16)
         chunks, nchunks, max_rows, gpw = plan[:4]
         ncd = plan[4] if len(plan) > 4 else None    # a fixed-capacity plan's device chunk count
         if bf16 and ncd is not None:
             gpw = 4   # (a fixed-capacity fp32 plan: its chunks run in passes of up to 512 pairs)
 
-        if wide:
+        if fam:
+            def launch():
+                N.check(lib.sgg_pool_fwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                            N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
+                                            scenes.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()),
+                        "sgg_pool_fwd_bn")
+            kname = lambda nch: "sgg::pool_fwd_bn_kernel"
+        elif wide:
             def launch():
                 N.check(lib.sgg_pool_fwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
                                               N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
@@ -1280,16 +1312,17 @@ class _Pool(torch.autograd.Function):
                             N.ptr(am), N.ptr(ncd), N.stream_ptr()), "sgg_pool_fwd")
             kname = lambda nch: _pool_kname(bn, gpw, nch, bf16, h.device, scenes.max_n, max_rows)
         nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn     # + the weights, once per launch (_pool_timing)
-        work = (scenes.S, B, _pool_flops(scenes, bn), nb)
+        # (the column-tiled forward forms the hidden units once per tile of 64 columns)
+        work = (scenes.S, B, _pool_flops_bn(scenes, bn) if fam else _pool_flops(scenes, bn), nb)
         rider = _PRIDER[0]
-        # (a wide forward is neither held nor carried: it never joins the paired launch)
-        if rider is not None and not wide and not rider.done and rider.held is None:
+        # (a wide or column-tiled forward is neither held nor carried: it never joins the paired launch)
+        if rider is not None and not tiled and not rider.done and rider.held is None:
             # the block's first pooling forward: held until the next one carries it
             batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
                                 gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
             rider.hold(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd), (A, W2, b2), bn, bf16, gpw,
                        nchunks, work, launch)
-        elif rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw, wide=wide):
+        elif rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw, wide=tiled):
             batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
                                 gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
             pl, (name, S2, B2, fl2, nb2, nch2) = rider.carry(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd),
@@ -1322,9 +1355,24 @@ class _Pool(torch.autograd.Function):
         P = bn * 512 + 1024 + bn
         dU = torch.empty(B, 512, device=h.device, dtype=torch.float32)
         wide = pool_is_wide(sc)
-        rows = lib.sgg_pool_bwd_wide_grid(sc.S, sc.max_n) if wide else lib.sgg_pool_bwd_grid(sc.S)
-        part = torch.empty(rows, P, device=h.device, dtype=torch.float32) if wgrad else None
+        fam = not pool_bn_built(bn)
+        if fam:
+            # the slab's rows, then the first launch's dA partials: the size the library reports
+            rows = lib.sgg_pool_bwd_bn_grid(sc.S, bn, sc.max_n)
+            nws = lib.sgg_pool_bwd_bn_ws_floats(sc.S, B, bn, sc.max_n)
+            if rows < 0 or nws < 0:
+                N.check(-1, "sgg_pool_bwd_bn_ws_floats")
+            part = torch.empty(nws, device=h.device, dtype=torch.float32) if wgrad else None
+        else:
+            rows = lib.sgg_pool_bwd_wide_grid(sc.S, sc.max_n) if wide else lib.sgg_pool_bwd_grid(sc.S)
+            part = torch.empty(rows, P, device=h.device, dtype=torch.float32) if wgrad else None
         def launch():
+            if fam:
+                N.check(lib.sgg_pool_bwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                            N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
+                                            N.ptr(part), part.numel() if wgrad else 0, N.stream_ptr()),
+                        "sgg_pool_bwd_bn")
+                return
             if wide:
                 N.check(lib.sgg_pool_bwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
                                               N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
@@ -1338,7 +1386,10 @@ class _Pool(torch.autograd.Function):
             nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * part.numel() if wgrad else 0.0)
             jq = max(1, min(8, 256 // sc.S)) if sc.S >= 1 else 1   # pool.hip pool_bwd_jq / launch_bwd
             stage = (sc.max_n + jq - 1) // jq + 1 <= 16
-            name = "sgg::pool_bwd_wide_kernel<%d, %s>" % (bn, "true" if wgrad else "false") if wide else \
+            # (the column-tiled family: its dU launch and, with weight gradients, its dW2 launch, timed together)
+            name = "sgg::pool_bwd_bn_du_kernel<%s>%s" % (("true", " + sgg::pool_bwd_bn_dw_kernel") if wgrad
+                                                        else ("false", "")) if fam else \
+                "sgg::pool_bwd_wide_kernel<%d, %s>" % (bn, "true" if wgrad else "false") if wide else \
                 "sgg::pool_bwd_kernel<%d, %s, %s>" % (bn, "true" if wgrad else "false", "true" if stage else "false")
             timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
         dh = None
@@ -1347,7 +1398,7 @@ class _Pool(torch.autograd.Function):
         # armed (social_pool): neither product is launched here -- the encoder's backward forms dh in its
         # prologue and carries the h^T dU partials (sgg_lstm_bwd_pooldh); what is returned as the gradient of
         # h is only the buffer by which that backward recognises its source
-        hand = ctx.pdh is not None and need[0] and not wide and (dual or not wgrad)
+        hand = ctx.pdh is not None and need[0] and not wide and not fam and (dual or not wgrad)
         if need[0]:
             base = ctx.link.take() if ctx.link is not None else None
             if hand:
@@ -1387,7 +1438,6 @@ class _Pool(torch.autograd.Function):
         # one launch after the dW1h partials: dW2, db2 (slab [dW2 | dA | db2]
         # row sums), dW1h = dU^T h, dc = sum_j dU_j, and the fold backward
         # of (dA, dc) -> dW1e, dWe, dbe
-        rows = part.shape[0]
         if (not dual and not hand) or (hand and ws is None):
             ws, splits = xtw_partial(h, dU, colsum=True)
         dW1 = torch.empty_like(W1)
@@ -1526,7 +1576,7 @@ def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, dh_in
     slot = None
     if dh_in_lstm and POOL_DH_IN_LSTM and U is not None and torch.is_grad_enabled():
         slot = getattr(U, "_sgg_pdh", None)
-        if slot is not None and (pool_is_wide(scenes)
+        if slot is not None and (pool_is_wide(scenes) or not pool_bn_built(W2.shape[0])
                                  or not _lib().sgg_lstm_bwd_pooldh_pays(h.numel() // h.shape[-1], h.shape[-1])):
             slot = None
     out, _ = _Pool.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, U, slot)

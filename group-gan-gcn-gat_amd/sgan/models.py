@@ -268,6 +268,9 @@ class PoolHiddenNet(nn.Module):
         if not self.fused_ok():
             raise NotImplementedError("the fused pooling kernel implements the reference configs "
                                       "(batch_norm=0, relu, dropout=0)")
+        if self.bottleneck_dim > K.POOL_BN_MAX:    # refused before any launch
+            raise K.N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
+                                "(SGG_POOL_BN_MAX)" % (self.bottleneck_dim, K.POOL_BN_MAX))
         sc = _scenes(seq_start_end, end_pos.device, scenes)
         l1, l2 = self.mlp_pre_pool[0], self.mlp_pre_pool[2]
         emb = self.spatial_embedding

@@ -78,16 +78,22 @@ class SceneIndex:
     POOL_WIDE_TARGET_CHUNKS = int(__import__("os").environ.get("SGG_POOL_WIDE_TARGET_CHUNKS", "2048"))
     POOL_MAX_GPW = int(__import__("os").environ.get("SGG_POOL_MAX_GPW", "0"))
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False, family_bn=False):
         """Device chunk table for sgg_pool_fwd (built on the host by
         sgg_pool_plan, cached per bottleneck width); bf16: the table of
         sgg_pool_fwd_bf16 (sgg_pool_plan_bf16: big chunks, one per CU);
         wide: the table of sgg_pool_fwd_wide (sgg_pool_plan_wide: scenes of
-        up to SGG_POOL_WIDE_MAX_PEDS peds, fp32 only)."""
+        up to SGG_POOL_WIDE_MAX_PEDS peds, fp32 only); family_bn: the table of
+        sgg_pool_fwd_bn (sgg_pool_plan_bn: any width up to SGG_POOL_BN_MAX,
+        every scene size, fp32 only -- the row chunks are shared by the
+        launch's column tiles, so the target is divided by their number)."""
+        if family_bn:
+            target_chunks = target_chunks or max(8, self.POOL_WIDE_TARGET_CHUNKS // ((bn + 63) // 64))
         target_chunks = target_chunks or (self.POOL_WIDE_TARGET_CHUNKS if wide else
                                           self.POOL_TARGET_CHUNKS_SMALL if bn <= 16 else self.POOL_TARGET_CHUNKS)
         plans = self.__dict__.setdefault("_pool_plans", {})
-        key = ("wide", bn, target_chunks) if wide else (bn, target_chunks, self.POOL_MAX_GPW, bool(bf16))
+        key = ("bn", bn, target_chunks) if family_bn else ("wide", bn, target_chunks) if wide else \
+            (bn, target_chunks, self.POOL_MAX_GPW, bool(bf16))
         if key not in plans:
             import ctypes
             lib = N.load()
@@ -95,7 +101,11 @@ class SceneIndex:
             cap = int(self.B) + self.S + 1
             tab = np.zeros((cap, 4), dtype=np.int32)
             mr, gpw = ctypes.c_int(0), ctypes.c_int(0)
-            if wide:
+            if family_bn:
+                nc = lib.sgg_pool_plan_bn(off.ctypes.data_as(ctypes.c_void_p), self.S, bn, target_chunks,
+                                          tab.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(mr),
+                                          ctypes.byref(gpw))
+            elif wide:
                 nc = lib.sgg_pool_plan_wide(off.ctypes.data_as(ctypes.c_void_p), self.S, bn, target_chunks,
                                             tab.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(mr),
                                             ctypes.byref(gpw))
@@ -272,11 +282,15 @@ class PaddedScenes(SceneIndex):
         """Offset of plan k: [chunk count, 0, 0, 0 | pool_cap x (scene, i0, i1, gpw)]."""
         return self._plan_base + (4 + 4 * self.pool_cap) * k
 
-    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False):
+    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False, family_bn=False):
         """(chunk table, grid basis, max rows, gpw, device chunk count): the
         table holds up to pool_cap chunks; the kernels walk the device count,
         the grid is sized by the chunk count of the batch that registered the
         plan (the capture's)."""
+        if family_bn or bn not in POOL_BUILT_BN:
+            # the padded-batch contract is pinned for the resident kernels only: refused before any launch
+            raise NotImplementedError("PaddedScenes: bottleneck_dim=%d is not one of the resident pooling kernels' "
+                                      "widths %s; padded batches run on those only" % (bn, POOL_BUILT_BN))
         for k, (r, b, gpw, grid) in enumerate(self._plans):
             if (r, b) == (rep, bn):
                 o = self._plan_region(k)
@@ -409,9 +423,9 @@ class _PaddedRepeat(SceneIndex):
     def ped_scene_long(self):
         raise NotImplementedError("PaddedScenes.repeat: no ped-scene map")
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, family_bn=False):
         # (the fixed-capacity plan serves both precisions: the bf16 kernel takes any chunk table)
-        return self.parent.pool_plan(bn, target_chunks, rep=self.k)
+        return self.parent.pool_plan(bn, target_chunks, rep=self.k, family_bn=family_bn)
 
     def groups(self, labels):
         raise NotImplementedError("PaddedScenes: the per-op group index is not captured")
@@ -421,6 +435,8 @@ SGG_POOL_MAX_PEDS = 64          # include/sgg.h: scene bound of the LDS-resident
 SGG_POOL_WIDE_MAX_PEDS = 1024   # include/sgg.h: scene bound of the tiled (wide) pooling kernels
 SGG_GAT_MAX_NODES = 128         # include/sgg.h: segment bound of the LDS-resident attention kernels
 SGG_GAT_WIDE_MAX_NODES = 1024   # include/sgg.h: segment bound of the tiled (wide) attention kernels
+SGG_POOL_BN_MAX = 1024          # include/sgg.h: bottleneck bound of the column-tiled pooling kernels
+POOL_BUILT_BN = (8, 16, 32, 48, 64)   # widths of the resident / wide pooling kernels (pool.hip, pool_wide.hip)
 SGG_POOL_MAX_ROWS = 64   # chunk height bound of sgg_pool_fwd (a padded plan's LDS is sized for it)
 
 

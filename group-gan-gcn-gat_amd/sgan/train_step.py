@@ -1028,6 +1028,12 @@ class BucketedGraphTrainer:
                     raise NotImplementedError("BucketedGraphTrainer: LSTM %s has hidden size H=%d; padded batches "
                                               "run on the four-wave LSTM kernels only (H in 16 / 32 / 48 / 64) -- "
                                               "use GanTrainer / GraphedTrainer" % (name, m.hidden_size))
+                if getattr(m, "mlp_pre_pool", None) is not None and not K.pool_bn_built(m.bottleneck_dim):
+                    # likewise pinned for the resident pooling kernels' widths only
+                    raise NotImplementedError("BucketedGraphTrainer: pooling net %s has bottleneck_dim=%d; padded "
+                                              "batches run on the resident pooling kernels only (bottleneck_dim in "
+                                              "8 / 16 / 32 / 48 / 64) -- use GanTrainer / GraphedTrainer"
+                                              % (name, m.bottleneck_dim))
         self.t, self.dd = trainer, ddset
         if pad_scenes < 1:
             # a full batch (S == batch_size) still needs one padding scene to

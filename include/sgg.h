@@ -41,6 +41,7 @@ const char* sgg_source_hash(void);
 /* Upper bounds the kernels are built for (checked on every call). */
 #define SGG_POOL_MAX_PEDS 64   /* peds per scene of the LDS-resident pooling kernels (sgg_pool_fwd*,
                                 * sgg_pool_bwd); larger scenes take the sgg_pool_*_wide entries    */
+#define SGG_POOL_BN_MAX 1024   /* largest bottleneck_dim of the column-tiled pooling kernels (sgg_pool_*_bn) */
 #define SGG_POOL_WIDE_MAX_PEDS 1024  /* peds per scene of the tiled pooling kernels (= the group
                                       * index's bound)                                             */
 #define SGG_GAT_MAX_NODES 128  /* nodes per segment held LDS-resident by the attention kernel */
@@ -200,6 +201,44 @@ int sgg_pool_bwd_wide(const float* U, const float* pos, const float* A, const fl
                       const float* out, const int32_t* argmax, const float* dout,
                       const int32_t* scene_off, int S, int B, int bn, int max_n,
                       float* dU, float* part, void* stream);
+
+/* Social pooling at any bottleneck_dim 1 <= bn <= SGG_POOL_BN_MAX, bn a
+ * runtime argument: the operands, outputs and argmax contract of
+ * sgg_pool_fwd_wide / sgg_pool_bwd_wide (fp32, scenes of 1 ..
+ * SGG_POOL_WIDE_MAX_PEDS peds, the same pair-space tiling), the 512 -> bn layer
+ * cut into column tiles of <= 64 columns.  W2, b2, out, argmax and dout have
+ * row stride bn.
+ * Forward: the chunk table comes from sgg_pool_plan_bn (sgg_pool_plan_wide's
+ * chunks at the 64-column tile's fixed *gpw).  Grid = chunks x column tiles;
+ * inside a tile a pair's value is computed exactly as sgg_pool_fwd_wide
+ * computes it at bn = 64, so out / argmax are bitwise that call's wherever
+ * both apply.
+ * Backward: two launches.  The first writes dU (every row; per entry the sum
+ * runs over column tiles ascending, then as sgg_pool_bwd_wide's -- bitwise
+ * its dU where both apply) and one dA partial per workgroup; the second
+ * writes the slab: sgg_pool_bwd_bn_grid(S, bn, max_n) rows of
+ * [dW2 | dA | db2] (bn*512 + 1024 + bn floats each), dW2 / db2 split over
+ * column groups and that many unit ranges, the dA partials folded into the
+ * rows in a fixed order.  part holds the slab rows followed by the dA
+ * partials: sgg_pool_bwd_bn_ws_floats(S, B, bn, max_n) floats in all, never
+ * more than 16 slab rows; part_floats is its size in floats.  part may be NULL
+ * (frozen weights): the first launch only, the same dU bitwise.  No
+ * floating-point atomics: every sum has a fixed order.
+ * Every bad argument -- a NULL operand, bn outside [1, SGG_POOL_BN_MAX], max_n
+ * outside [1, SGG_POOL_WIDE_MAX_PEDS], a workspace smaller than reported -- is
+ * SGG_E_ARG (also from the two size functions) and nothing is launched. */
+int sgg_pool_plan_bn(const int32_t* host_scene_off, int S, int bn, int target_chunks, int32_t* host_chunks,
+                     int cap, int* max_rows, int* gpw);
+int sgg_pool_fwd_bn(const float* U, const float* pos, const float* A, const float* W2,
+                    const float* b2, const int32_t* scene_off, const int32_t* chunks, int nchunks,
+                    int max_rows, int gpw, int B, int bn, int max_n, float* out, int32_t* argmax,
+                    void* stream);
+int sgg_pool_bwd_bn_grid(int S, int bn, int max_n);
+long long sgg_pool_bwd_bn_ws_floats(int S, int B, int bn, int max_n);
+int sgg_pool_bwd_bn(const float* U, const float* pos, const float* A, const float* W2,
+                    const float* out, const int32_t* argmax, const float* dout,
+                    const int32_t* scene_off, int S, int B, int bn, int max_n,
+                    float* dU, float* part, size_t part_floats, void* stream);
 
 /* ------------------------------------------------------------------------
  * Graph attention over the nodes of each segment (GraphAttentionLayer,

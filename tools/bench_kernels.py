@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|gatwide|gatdrop|...]
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|poolbn|gatwide|gatdrop|...]
 validate [a|b]: wall time of one check_accuracy pass, three routes; valkernel: sgg_val_metrics alone."""
 import os
 import sys
@@ -97,6 +97,60 @@ def poolwide(S, n, bn, reps=20):
         print("pool %-8s S=%3d n=%4d bn=%2d chunks=%5d rows=%2d gpw=%d  fwd %8.1f us %6.1f TF/s %5.3f ns/pair  "
               "bwd %8.1f us" % (name, S, n, bn, nchunks, max_rows, g, uf, flops / uf / 1e6, uf * 1e3 / (S * n * n), ub),
               flush=True)
+
+
+def poolbn(S, n, bn, reps=20):
+    """The column-tiled pooling forward and backward (sgg_pool_fwd_bn /
+    sgg_pool_bwd_bn, any bottleneck_dim up to 1024) on S scenes of n peds; at
+    bn = 64 the wide kernels (sgg_pool_fwd_wide / sgg_pool_bwd_wide) on the
+    same operands next to them.  Backward: with weight gradients (both
+    launches) and with part = NULL (the dU launch alone)."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B = S * n
+    sc = SceneIndex(np.arange(0, B + 1, n), dev)
+    U = torch.randn(B, 512, device=dev) * 0.3
+    pos = torch.rand(B, 2, device=dev) * 15
+    A = torch.randn(512, 2, device=dev) * 0.3
+    W2 = torch.randn(bn, 512, device=dev) * 0.05
+    b2 = torch.randn(bn, device=dev) * 0.1
+    dout = torch.randn(B, bn, device=dev)
+    lib = N.load()
+    tiles = (bn + 63) // 64
+    flops = float(S * n * n) * 512 * (4 * tiles + 2 * bn)
+    out = torch.empty(B, bn, device=dev)
+    am = torch.empty(B, bn, device=dev, dtype=torch.int32)
+    dU = torch.empty(B, 512, device=dev)
+    P = bn * 512 + 1024 + bn
+    for name in ["bn"] + (["wide"] if bn == 64 else []):
+        if name == "bn":
+            chunks, nchunks, max_rows, g = sc.pool_plan(bn, family_bn=True)
+            fwd = lambda: N.check(lib.sgg_pool_fwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                                      N.ptr(sc.scene_off), N.ptr(chunks), nchunks, max_rows, g, B, bn,
+                                                      sc.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()), "fwd")
+            part = torch.empty(lib.sgg_pool_bwd_bn_ws_floats(S, B, bn, n), device=dev)
+            bwd_p = lambda p, nf: N.check(lib.sgg_pool_bwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out),
+                                                              N.ptr(am), N.ptr(dout), N.ptr(sc.scene_off), S, B, bn,
+                                                              sc.max_n, N.ptr(dU), N.ptr(p), nf, N.stream_ptr()),
+                                          "bwd")
+            bwd, bwd0 = (lambda: bwd_p(part, part.numel())), (lambda: bwd_p(None, 0))
+        else:
+            chunks, nchunks, max_rows, g = sc.pool_plan(bn, wide=True)
+            fwd = lambda: N.check(lib.sgg_pool_fwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                                        N.ptr(sc.scene_off), N.ptr(chunks), nchunks, max_rows, g, B,
+                                                        bn, sc.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()), "fwd")
+            part = torch.empty(lib.sgg_pool_bwd_wide_grid(S, n), P, device=dev)
+            bwd_p = lambda p: N.check(lib.sgg_pool_bwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out),
+                                                            N.ptr(am), N.ptr(dout), N.ptr(sc.scene_off), S, B, bn,
+                                                            sc.max_n, N.ptr(dU), N.ptr(p), N.stream_ptr()), "bwd")
+            bwd, bwd0 = (lambda: bwd_p(part)), (lambda: bwd_p(None))
+        uf = timeit(fwd, reps)
+        ub = timeit(bwd, reps)
+        ub0 = timeit(bwd0, reps)
+        print("pool %-4s S=%3d n=%4d bn=%4d tiles=%2d chunks=%5d rows=%2d  fwd %8.1f us %6.1f TF/s %6.3f ns/pair  "
+              "bwd %8.1f us  bwd(dU only) %8.1f us  ws %.1f MB" % (
+                  name, S, n, bn, tiles, nchunks, max_rows, uf, flops / uf / 1e6, uf * 1e3 / (S * n * n), ub, ub0,
+                  part.numel() * 4 / 1e6), flush=True)
 
 
 def gatwide(S, n, heads, F, reps=20):
@@ -415,6 +469,11 @@ if __name__ == "__main__":
             # (64 x 128: enough rows for chunks above gpw rows -- several passes per j-tile)
             for (S, n) in ((64, 64), (32, 128), (8, 256), (1, 1024), (64, 128)):
                 poolwide(S, n, bn)
+        sys.exit(0)
+    if what == "poolbn":   # the column-tiled pooling kernels: bn 64 next to the wide kernels, 2 and 16 tiles
+        for (S, n) in ((64, 20), (512, 20)):
+            for bn in (64, 128, 1024):
+                poolbn(S, n, bn)
         sys.exit(0)
     if what == "gatwide":   # the tiled attention kernels above 128 nodes, next to the resident ones at 128
         for (S, n) in ((32, 128), (8, 256), (1, 1024)):
