@@ -17,6 +17,7 @@
 // takes.  Rows past B compute on a clamped (valid) row and store nothing.
 #include "sgg_common.h"
 #include "xw_body.h"
+#include "pool_drop.h"
 
 namespace sgg {
 
@@ -323,71 +324,13 @@ __global__ void __launch_bounds__(256) dec_step_bwd_kernel(SggDecStepBwd a) {
   }
 }
 
-// The pooling's gradient of the positions (sgg.h sgg_pool_dpos): one wave per
-// ped r, the lanes over the 512 hidden units.  q(i, c) = g(i, c) sum_k W2[c, k]
-// [hidden(i, j*, k) > 0] A[k, :] with j* = argmax[i, c] and g = dout where
-// out > 0; dpos[r] = sum over the (i, c) of r's scene with j* = r, ascending,
-// of q(i, c), minus sum_c q(r, c).
-__global__ void __launch_bounds__(256) pool_dpos_kernel(const float* __restrict__ U, const float* __restrict__ pos,
-                                                        const float* __restrict__ A, const float* __restrict__ W2,
-                                                        const float* __restrict__ out,
-                                                        const int32_t* __restrict__ am,
-                                                        const float* __restrict__ dout,
-                                                        const int32_t* __restrict__ scene_off, int S, int B, int bn,
-                                                        float* __restrict__ dpos) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= B) return;
-  // the scene of r: the last s with scene_off[s] <= r
-  int lo = 0, hi = S - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (scene_off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  const int i0 = scene_off[lo], i1 = scene_off[lo + 1];
-  float a0[kHidden / 64], a1[kHidden / 64];
-#pragma unroll
-  for (int q = 0; q < kHidden / 64; ++q) {
-    a0[q] = A[2 * (lane + 64 * q)];
-    a1[q] = A[2 * (lane + 64 * q) + 1];
-  }
-  float sx = 0.f, sy = 0.f;   // identical in every lane
-  // one (i, c) pair's q, times sign
-  auto pair = [&](int i, int c, float sign) {
-    const size_t o = (size_t)i * bn + c;
-    const float g = out[o] > 0.f ? dout[o] : 0.f;
-    if (g == 0.f) return;
-    const int j = am[o];
-    const float dx = pos[2 * j] - pos[2 * i], dy = pos[2 * j + 1] - pos[2 * i + 1];
-    float px = 0.f, py = 0.f;
-#pragma unroll
-    for (int q = 0; q < kHidden / 64; ++q) {
-      const int k = lane + 64 * q;
-      const float pre = fmaf(a1[q], dy, fmaf(a0[q], dx, U[(size_t)j * kHidden + k]));
-      const float w = keep_if(W2[(size_t)c * kHidden + k], pre > 0.f);
-      px = fmaf(w, a0[q], px);
-      py = fmaf(w, a1[q], py);
-    }
-    sx = fmaf(sign * g, wave_sum(px), sx);
-    sy = fmaf(sign * g, wave_sum(py), sy);
-  };
-  const int e0 = i0 * bn, e1 = i1 * bn;
-  for (int base = e0; base < e1; base += 64) {
-    const int e = base + lane;
-    unsigned long long hits = __ballot(e < e1 && am[min(e, e1 - 1)] == r);
-    while (hits) {
-      const int b = __ffsll((long long)hits) - 1;
-      hits &= hits - 1;
-      const int eh = base + b;
-      pair(eh / bn, eh % bn, 1.f);
-    }
-  }
-  for (int c = 0; c < bn; ++c) pair(r, c, -1.f);
-  if (lane == 0) {
-    dpos[2 * r] = sx;
-    dpos[2 * r + 1] = sy;
-  }
-}
+// pool_dpos_kernel and its dropout form pool_dpos_drop_kernel: one text (pool_dpos_kernel.h) compiled twice
+#define SGG_POOL_DROP 0
+#include "pool_dpos_kernel.h"
+#undef SGG_POOL_DROP
+#define SGG_POOL_DROP 1
+#include "pool_dpos_kernel.h"
+#undef SGG_POOL_DROP
 
 static bool ds_cell_ok(int H, int NU) { return H >= 16 && H <= 64 && H % 16 == 0 && (NU == 0 || NU == kHidden); }
 static bool ds_mlp_ok(int H, int bn, int D) { return bn >= 1 && H + bn <= kDsMaxCols && D >= 1 && D <= kDsMaxCols; }
@@ -452,6 +395,21 @@ int sgg_pool_dpos(const float* U, const float* pos, const float* A, const float*
   hipLaunchKernelGGL(sgg::pool_dpos_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, U, pos, A, W2, out,
                      argmax, dout, scene_off, S, B, bn, dpos);
   SGG_RETURN_LAUNCH("sgg_pool_dpos");
+}
+
+int sgg_pool_dpos_drop(const float* U, const float* pos, const float* A, const float* W2, const float* out,
+                       const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
+                       float* dpos, float p, unsigned long long seed, unsigned offset,
+                       const unsigned long long* rng_dev, void* stream) {
+  SGG_CHECK_ARG(U && pos && A && W2 && out && argmax && dout && scene_off && dpos, "sgg_pool_dpos_drop: NULL operand");
+  SGG_CHECK_ARG(S >= 1 && B >= 0 && bn >= 1 && bn <= SGG_POOL_BN_MAX, "sgg_pool_dpos_drop: S = %d, B = %d, bn = %d (1 .. %d)",
+                S, B, bn, SGG_POOL_BN_MAX);
+  sgg::DropArgs d;
+  if (!sgg::pool_drop_args("sgg_pool_dpos_drop", p, seed, offset, rng_dev, &d)) return SGG_E_ARG;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(sgg::pool_dpos_drop_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, U, pos, A, W2,
+                     out, argmax, dout, scene_off, S, B, bn, dpos, d);
+  SGG_RETURN_LAUNCH("sgg_pool_dpos_drop");
 }
 
 }  // extern "C"

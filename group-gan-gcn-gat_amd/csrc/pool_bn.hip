@@ -6,6 +6,7 @@
 #include "sgg_common.h"
 #include "pool_common.h"
 #include "pool_tiled_fwd.h"
+#include "pool_drop.h"
 
 namespace sgg {
 
@@ -30,6 +31,18 @@ __global__ void __launch_bounds__(256) pool_fwd_bn_kernel(
   // (grid.y = ceil(bn / 64): every tile has at least one live column)
   pool_fwd_tiled_body<kBT, kBGPW, true>(U, pos, A, W2, b2, scene_off, chunks, nch, out, argmax,
                                         (int)blockIdx.y * kBT, bn);
+}
+
+// The dropout form (sgg_pool_fwd_bn_drop): the same body with the two scaled masks of pool_drop.h -- the
+// hidden value m1 * relu(u + a . rel), the epilogue value m2 * relu(acc + b2) -- both functions of
+// (i, j, column) alone, so every column tile forms the same hidden units.
+__global__ void __launch_bounds__(256) pool_fwd_bn_drop_kernel(
+    const float* __restrict__ U, const float* __restrict__ pos, const float* __restrict__ A,
+    const float* __restrict__ W2 /* bn x 512 */, const float* __restrict__ b2,
+    const int32_t* __restrict__ scene_off, const int4* __restrict__ chunks, int nch, int bn,
+    float* __restrict__ out, int32_t* __restrict__ argmax, DropArgs drop) {
+  pool_fwd_tiled_body<kBT, kBGPW, true, true>(U, pos, A, W2, b2, scene_off, chunks, nch, out, argmax,
+                                              (int)blockIdx.y * kBT, bn, drop);
 }
 
 // ---- backward -----------------------------------------------------------------
@@ -57,214 +70,14 @@ constexpr int kBJR = 16;     // peds of a j range (pool_wide.hip kWideJR)
 constexpr int kBCG = 16;     // columns of a dW2 workgroup
 constexpr int kBRows = 8;    // rows of the parameter-gradient slab
 
-template <bool WGRAD>
-__global__ void __launch_bounds__(512) pool_bwd_bn_du_kernel(
-    const float* __restrict__ U, const float* __restrict__ pos, const float* __restrict__ A,
-    const float* __restrict__ W2 /* bn x 512 */, const float* __restrict__ out,
-    const int32_t* __restrict__ argmax, const float* __restrict__ dout, const int32_t* __restrict__ scene_off,
-    int S, int jq, int bn, float* __restrict__ dU, float* __restrict__ dAp /* grid x 1024 */) {
-  constexpr int BN = kBT;
-  __shared__ unsigned long long msk[kBJR * BN];   // (j - j0, c) -> set of i of the tile
-  __shared__ float gs[64 * BN];                   // masked dout (i, c) of the tile
-  __shared__ float2 ps[SGG_POOL_WIDE_MAX_PEDS];
-  __shared__ float Us[kBJR * kHid];               // rows j0 .. j1 of U
-  __shared__ float dUs[kBJR * kHid];              // their gradient, summed over column and i tiles
-  const int k = threadIdx.x;   // hidden unit, blockDim.x == 512
-  const int nct = (bn + BN - 1) / BN;
-  float w2[BN];
-  int have = -1;               // the column tile whose W2 rows sit in w2
-  const float a0 = A[2 * k], a1 = A[2 * k + 1];
-  float dA0 = 0.f, dA1 = 0.f;
-  for (int un = blockIdx.x; un < S * jq; un += gridDim.x) {
-    const int s = un / jq, jp = un - s * jq;
-    const int o = scene_off[s];
-    const int n = scene_off[s + 1] - o;
-    const int j0 = (int)(((long long)n * jp) / jq), j1 = (int)(((long long)n * (jp + 1)) / jq);
-    if (j1 <= j0) continue;   // an empty range (n < jq), uniform over the workgroup
-    const int nr = j1 - j0;   // <= kBJR (host: jq >= ceil(max_n / kBJR))
-    {
-      const float* Ur = U + (size_t)(o + j0) * kHid + k;
-#pragma unroll 4
-      for (int r = 0; r < nr; ++r) {
-        Us[r * kHid + k] = Ur[(size_t)r * kHid];
-        dUs[r * kHid + k] = 0.f;
-      }
-    }
-    for (int q = k; q < n; q += kHid) ps[q] = make_float2(pos[2 * (o + q)], pos[2 * (o + q) + 1]);
-    for (int ct = 0; ct < nct; ++ct) {
-      const int cb = ct * BN;
-      const int nc = min(BN, bn - cb);
-      if (ct != have) {
-#pragma unroll
-        for (int c = 0; c < BN; ++c) w2[c] = c < nc ? W2[(size_t)(cb + c) * kHid + k] : 0.f;
-        have = ct;
-      }
-      for (int t0 = 0; t0 < n; t0 += 64) {
-        const int ni = min(64, n - t0);
-        const int ne = ni * BN;
-        for (int e = k; e < kBJR * BN; e += kHid) msk[e] = 0ull;
-        __syncthreads();   // masks cleared before the ORs; the unit's ps written
-#pragma unroll 2
-        for (int e = k; e < ne; e += kHid) {
-          const int i = e / BN, c = e - i * BN;
-          if (c < nc) {
-            const size_t ge = (size_t)(o + t0 + i) * bn + cb + c;
-            const float ov = out[ge], dv = dout[ge];
-            const int jl = argmax[ge] - o - j0;
-            const float g = ov > 0.f ? dv : 0.f;
-            gs[e] = g;
-            if (g != 0.f && jl >= 0 && jl < nr) atomicOr(&msk[jl * BN + c], 1ull << i);
-          }
-        }
-        __syncthreads();
-        for (int r = 0; r < nr; ++r) {
-          const float u = Us[r * kHid + k];
-          const float2 pj = ps[j0 + r];
-          float du = dUs[r * kHid + k];
-          constexpr int CB = 16;
-          unsigned long long mrow[CB];
-#pragma unroll
-          for (int c = 0; c < BN; ++c) {
-            if (c % CB == 0) {
-#pragma unroll
-              for (int cc = 0; cc < CB; ++cc) mrow[cc] = msk[r * BN + c + cc];
-            }
-            const unsigned long long mv = mrow[c % CB];
-            const unsigned mhi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(mv >> 32));
-            const unsigned mlo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)mv);
-            unsigned long long m = ((unsigned long long)mhi << 32) | (unsigned long long)mlo;
-            // two set bits per trip, taken in ascending i one at a time (pool_bwd_wide_kernel)
-            auto entry = [&](float g, float2 pi) {
-              const float rx = pj.x - pi.x, ry = pj.y - pi.y;
-              const float pre = fmaf(a1, ry, fmaf(a0, rx, u));
-              const float gm = pre > 0.f ? g : 0.f;
-              const float d = gm * w2[c];
-              du += d;
-              if (WGRAD) {
-                dA0 = fmaf(d, rx, dA0);
-                dA1 = fmaf(d, ry, dA1);
-              }
-            };
-            while (m) {
-              const int i = __builtin_ctzll(m);
-              m &= m - 1;
-              const bool two = m != 0;   // uniform
-              const int i2 = two ? __builtin_ctzll(m) : i;
-              if (two) m &= m - 1;
-              const float g = gs[i * BN + c], g2 = gs[i2 * BN + c];
-              const float2 pi = ps[t0 + i], pi2 = ps[t0 + i2];
-              entry(g, pi);
-              if (two) entry(g2, pi2);
-            }
-          }
-          dUs[r * kHid + k] = du;
-        }
-        __syncthreads();   // the walk is done: msk / gs (and, after the last tile, ps) may be rewritten
-      }
-    }
-    for (int r = 0; r < nr; ++r) dU[(size_t)(o + j0 + r) * kHid + k] = dUs[r * kHid + k];
-  }
-  if (WGRAD) {
-    dAp[(size_t)blockIdx.x * 2 * kHid + 2 * k] = dA0;
-    dAp[(size_t)blockIdx.x * 2 * kHid + 2 * k + 1] = dA1;
-  }
-}
-
-__global__ void __launch_bounds__(512) pool_bwd_bn_dw_kernel(
-    const float* __restrict__ U, const float* __restrict__ pos, const float* __restrict__ A,
-    const float* __restrict__ out, const int32_t* __restrict__ argmax, const float* __restrict__ dout,
-    const int32_t* __restrict__ scene_off, int S, int jq, int bn, const float* __restrict__ dAp, int ndA,
-    float* __restrict__ part /* kBRows x (bn*512 + 1024 + bn) */) {
-  constexpr int CG = kBCG;
-  __shared__ unsigned long long msk[kBJR * CG];
-  __shared__ float gs[64 * CG];
-  __shared__ float2 ps[SGG_POOL_WIDE_MAX_PEDS];
-  __shared__ float Us[kBJR * kHid];
-  const int k = threadIdx.x;   // hidden unit, blockDim.x == 512
-  const int cb = (int)blockIdx.x * CG;
-  const int nc = min(CG, bn - cb);   // >= 1: grid.x = ceil(bn / CG)
-  const int row = (int)blockIdx.y;
-  float dw2[CG];
-#pragma unroll
-  for (int c = 0; c < CG; ++c) dw2[c] = 0.f;
-  const float a0 = A[2 * k], a1 = A[2 * k + 1];
-  float db2 = 0.f;
-  for (int un = row; un < S * jq; un += kBRows) {
-    const int s = un / jq, jp = un - s * jq;
-    const int o = scene_off[s];
-    const int n = scene_off[s + 1] - o;
-    const int j0 = (int)(((long long)n * jp) / jq), j1 = (int)(((long long)n * (jp + 1)) / jq);
-    if (j1 <= j0) continue;
-    const int nr = j1 - j0;
-    {
-      const float* Ur = U + (size_t)(o + j0) * kHid + k;
-#pragma unroll 4
-      for (int r = 0; r < nr; ++r) Us[r * kHid + k] = Ur[(size_t)r * kHid];
-    }
-    for (int q = k; q < n; q += kHid) ps[q] = make_float2(pos[2 * (o + q)], pos[2 * (o + q) + 1]);
-    for (int t0 = 0; t0 < n; t0 += 64) {
-      const int ni = min(64, n - t0);
-      const int ne = ni * CG;
-      for (int e = k; e < kBJR * CG; e += kHid) msk[e] = 0ull;
-      __syncthreads();
-      for (int e = k; e < ne; e += kHid) {
-        const int i = e / CG, c = e - i * CG;
-        float g = 0.f;
-        if (c < nc) {
-          const size_t ge = (size_t)(o + t0 + i) * bn + cb + c;
-          const float ov = out[ge], dv = dout[ge];
-          const int jl = argmax[ge] - o - j0;
-          g = ov > 0.f ? dv : 0.f;
-          if (g != 0.f && jl >= 0 && jl < nr) atomicOr(&msk[jl * CG + c], 1ull << i);
-        }
-        gs[e] = g;
-      }
-      __syncthreads();
-      // db2 once per scene: by the unit of the scene's last (never empty) range
-      if (jp == jq - 1 && k < nc)
-        for (int i = 0; i < ni; ++i) db2 += gs[i * CG + k];
-      for (int r = 0; r < nr; ++r) {
-        const float u = Us[r * kHid + k];
-        const float2 pj = ps[j0 + r];
-        unsigned long long mrow[CG];
-#pragma unroll
-        for (int c = 0; c < CG; ++c) mrow[c] = msk[r * CG + c];
-#pragma unroll
-        for (int c = 0; c < CG; ++c) {
-          const unsigned mhi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(mrow[c] >> 32));
-          const unsigned mlo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)mrow[c]);
-          unsigned long long m = ((unsigned long long)mhi << 32) | (unsigned long long)mlo;
-          while (m) {   // ascending i
-            const int i = __builtin_ctzll(m);
-            m &= m - 1;
-            const float g = gs[i * CG + c];
-            const float2 pi = ps[t0 + i];
-            const float rx = pj.x - pi.x, ry = pj.y - pi.y;
-            const float pre = fmaf(a1, ry, fmaf(a0, rx, u));
-            const float gm = pre > 0.f ? g : 0.f;
-            dw2[c] = fmaf(gm, pre, dw2[c]);
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // row `row` of the slab [dW2 (bn x 512) | dA (512 x 2) | db2 (bn)]: this workgroup's columns
-  float* prow = part + (size_t)row * ((size_t)bn * kHid + 2 * kHid + bn);
-#pragma unroll
-  for (int c = 0; c < CG; ++c)
-    if (c < nc) prow[(size_t)(cb + c) * kHid + k] = dw2[c];
-  if (k < nc) prow[(size_t)bn * kHid + 2 * kHid + cb + k] = db2;
-  if (blockIdx.x == 0) {
-    float s0 = 0.f, s1 = 0.f;
-    for (int g = row; g < ndA; g += kBRows) {
-      s0 += dAp[(size_t)g * 2 * kHid + 2 * k];
-      s1 += dAp[(size_t)g * 2 * kHid + 2 * k + 1];
-    }
-    prow[(size_t)bn * kHid + 2 * k] = s0;
-    prow[(size_t)bn * kHid + 2 * k + 1] = s1;
-  }
-}
+// pool_bwd_bn_du_kernel<WGRAD> / pool_bwd_bn_dw_kernel and their dropout forms: one text
+// (pool_bn_bwd.h) compiled twice
+#define SGG_POOL_DROP 0
+#include "pool_bn_bwd.h"
+#undef SGG_POOL_DROP
+#define SGG_POOL_DROP 1
+#include "pool_bn_bwd.h"
+#undef SGG_POOL_DROP
 
 // j ranges per scene (pool_wide.hip wide_bwd_jq): a range fits the LDS rows,
 // more ranges while S x jq stays within one round of the chip
@@ -315,14 +128,15 @@ extern "C" int sgg_pool_plan_bn(const int32_t* host_scene_off, int S, int bn, in
   return pool_plan_rows("sgg_pool_plan_bn", host_scene_off, S, kBGPW, target_chunks, chunks, cap, max_rows, gpw_out);
 }
 
-extern "C" int sgg_pool_fwd_bn(const float* U, const float* pos, const float* A, const float* W2, const float* b2,
-                               const int32_t* scene_off, const int32_t* chunks, int nchunks, int max_rows, int gpw,
-                               int B, int bn, int max_n, float* out, int32_t* argmax, void* stream) {
-  SGG_CHECK_ARG(U && pos && A && W2 && b2 && scene_off && chunks && out && argmax, "sgg_pool_fwd_bn: null pointer");
-  if (!bn_sizes_ok("sgg_pool_fwd_bn", bn, max_n)) return SGG_E_ARG;
-  SGG_CHECK_ARG(nchunks >= 0 && B >= 0, "sgg_pool_fwd_bn: bad sizes");
-  SGG_CHECK_ARG(max_rows >= 1 && max_rows <= 64, "sgg_pool_fwd_bn: chunk rows %d outside [1, 64]", max_rows);
-  SGG_CHECK_ARG(gpw == kBGPW, "sgg_pool_fwd_bn: gpw %d is not sgg_pool_plan_bn's (%d)", gpw, kBGPW);
+// sgg_pool_fwd_bn (drop == NULL) and sgg_pool_fwd_bn_drop: the same checks, grid and LDS
+static int fwd_bn(const char* name, const float* U, const float* pos, const float* A, const float* W2, const float* b2,
+                  const int32_t* scene_off, const int32_t* chunks, int nchunks, int max_rows, int gpw, int B, int bn,
+                  int max_n, float* out, int32_t* argmax, const DropArgs* drop, void* stream) {
+  SGG_CHECK_ARG(U && pos && A && W2 && b2 && scene_off && chunks && out && argmax, "%s: null pointer", name);
+  if (!bn_sizes_ok(name, bn, max_n)) return SGG_E_ARG;
+  SGG_CHECK_ARG(nchunks >= 0 && B >= 0, "%s: bad sizes", name);
+  SGG_CHECK_ARG(max_rows >= 1 && max_rows <= 64, "%s: chunk rows %d outside [1, 64]", name, max_rows);
+  SGG_CHECK_ARG(gpw == kBGPW, "%s: gpw %d is not sgg_pool_plan_bn's (%d)", name, gpw, kBGPW);
   if (nchunks == 0) return 0;
   // x: a multiple of 8 workgroups (XCD-aware order), x * y at most about four rounds of the chip
   const int nct = (bn + kBT - 1) / kBT;
@@ -330,9 +144,32 @@ extern "C" int sgg_pool_fwd_bn(const float* U, const float* pos, const float* A,
   int cap = (4 * device_cus() / nct + 7) & ~7;
   if (cap < 8) cap = 8;
   if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(pool_fwd_bn_kernel, dim3(grid, nct), dim3(256), pool_fwd_tiled_lds<kBT>(max_rows), (hipStream_t)stream, U, pos,
-                     A, W2, b2, scene_off, reinterpret_cast<const int4*>(chunks), nchunks, bn, out, argmax);
-  SGG_RETURN_LAUNCH("sgg_pool_fwd_bn");
+  if (drop)
+    hipLaunchKernelGGL(pool_fwd_bn_drop_kernel, dim3(grid, nct), dim3(256), pool_fwd_tiled_lds<kBT>(max_rows),
+                       (hipStream_t)stream, U, pos, A, W2, b2, scene_off, reinterpret_cast<const int4*>(chunks), nchunks,
+                       bn, out, argmax, *drop);
+  else
+    hipLaunchKernelGGL(pool_fwd_bn_kernel, dim3(grid, nct), dim3(256), pool_fwd_tiled_lds<kBT>(max_rows), (hipStream_t)stream, U, pos,
+                       A, W2, b2, scene_off, reinterpret_cast<const int4*>(chunks), nchunks, bn, out, argmax);
+  SGG_RETURN_LAUNCH(name);
+}
+
+extern "C" int sgg_pool_fwd_bn(const float* U, const float* pos, const float* A, const float* W2, const float* b2,
+                               const int32_t* scene_off, const int32_t* chunks, int nchunks, int max_rows, int gpw,
+                               int B, int bn, int max_n, float* out, int32_t* argmax, void* stream) {
+  return fwd_bn("sgg_pool_fwd_bn", U, pos, A, W2, b2, scene_off, chunks, nchunks, max_rows, gpw, B, bn, max_n, out,
+                argmax, nullptr, stream);
+}
+
+extern "C" int sgg_pool_fwd_bn_drop(const float* U, const float* pos, const float* A, const float* W2, const float* b2,
+                                    const int32_t* scene_off, const int32_t* chunks, int nchunks, int max_rows,
+                                    int gpw, int B, int bn, int max_n, float* out, int32_t* argmax, float p,
+                                    unsigned long long seed, unsigned offset, const unsigned long long* rng_dev,
+                                    void* stream) {
+  DropArgs d;
+  if (!pool_drop_args("sgg_pool_fwd_bn_drop", p, seed, offset, rng_dev, &d)) return SGG_E_ARG;
+  return fwd_bn("sgg_pool_fwd_bn_drop", U, pos, A, W2, b2, scene_off, chunks, nchunks, max_rows, gpw, B, bn, max_n, out,
+                argmax, &d, stream);
 }
 
 extern "C" int sgg_pool_bwd_bn_grid(int S, int bn, int max_n) {
@@ -350,21 +187,28 @@ extern "C" long long sgg_pool_bwd_bn_ws_floats(int S, int B, int bn, int max_n) 
   return kBRows * bn_slab_cols(bn) + (long long)bn_bwd_du_grid(S, bn, max_n) * 2 * kHid;
 }
 
-extern "C" int sgg_pool_bwd_bn(const float* U, const float* pos, const float* A, const float* W2, const float* out,
-                               const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
-                               int max_n, float* dU, float* part, size_t part_floats, void* stream) {
-  SGG_CHECK_ARG(U && pos && A && W2 && out && argmax && dout && scene_off && dU, "sgg_pool_bwd_bn: null pointer");
-  if (!bn_sizes_ok("sgg_pool_bwd_bn", bn, max_n)) return SGG_E_ARG;
-  SGG_CHECK_ARG(S >= 0 && B >= 0, "sgg_pool_bwd_bn: bad sizes");
+// sgg_pool_bwd_bn (drop == NULL) and sgg_pool_bwd_bn_drop: the same checks, grids and workspace
+static int bwd_bn(const char* name, const float* U, const float* pos, const float* A, const float* W2, const float* out,
+                  const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn, int max_n,
+                  float* dU, float* part, size_t part_floats, const DropArgs* drop, void* stream) {
+  SGG_CHECK_ARG(U && pos && A && W2 && out && argmax && dout && scene_off && dU, "%s: null pointer", name);
+  if (!bn_sizes_ok(name, bn, max_n)) return SGG_E_ARG;
+  SGG_CHECK_ARG(S >= 0 && B >= 0, "%s: bad sizes", name);
   const long long need = sgg_pool_bwd_bn_ws_floats(S, B, bn, max_n);
   SGG_CHECK_ARG(!part || (long long)part_floats >= need,
-                "sgg_pool_bwd_bn: workspace of %zu floats, sgg_pool_bwd_bn_ws_floats asks for %lld", part_floats, need);
+                "%s: workspace of %zu floats, sgg_pool_bwd_bn_ws_floats asks for %lld", name, part_floats, need);
   hipStream_t st = (hipStream_t)stream;
   if (S == 0) return 0;
   const int jq = bn_bwd_jq(S, max_n);
   const int grid = bn_bwd_du_grid(S, bn, max_n);
   float* dAp = part ? part + (size_t)kBRows * bn_slab_cols(bn) : nullptr;
-  if (part)
+  if (drop && part)
+    hipLaunchKernelGGL(pool_bwd_bn_du_drop_kernel<true>, dim3(grid), dim3(512), 0, st, U, pos, A, W2, out, argmax, dout,
+                       scene_off, S, jq, bn, dU, dAp, *drop);
+  else if (drop)
+    hipLaunchKernelGGL(pool_bwd_bn_du_drop_kernel<false>, dim3(grid), dim3(512), 0, st, U, pos, A, W2, out, argmax,
+                       dout, scene_off, S, jq, bn, dU, dAp, *drop);
+  else if (part)
     hipLaunchKernelGGL(pool_bwd_bn_du_kernel<true>, dim3(grid), dim3(512), 0, st, U, pos, A, W2, out, argmax, dout,
                        scene_off, S, jq, bn, dU, dAp);
   else
@@ -373,12 +217,34 @@ extern "C" int sgg_pool_bwd_bn(const float* U, const float* pos, const float* A,
   {
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) {
-      sgg::set_error("sgg_pool_bwd_bn: launch failed: %s", hipGetErrorString(e_));
+      sgg::set_error("%s: launch failed: %s", name, hipGetErrorString(e_));
       return (int)e_;
     }
   }
   if (!part) return 0;
-  hipLaunchKernelGGL(pool_bwd_bn_dw_kernel, dim3((bn + kBCG - 1) / kBCG, kBRows), dim3(512), 0, st, U, pos, A, out,
-                     argmax, dout, scene_off, S, jq, bn, dAp, grid, part);
-  SGG_RETURN_LAUNCH("sgg_pool_bwd_bn");
+  if (drop)
+    hipLaunchKernelGGL(pool_bwd_bn_dw_drop_kernel, dim3((bn + kBCG - 1) / kBCG, kBRows), dim3(512), 0, st, U, pos, A,
+                       out, argmax, dout, scene_off, S, jq, bn, dAp, grid, part, *drop);
+  else
+    hipLaunchKernelGGL(pool_bwd_bn_dw_kernel, dim3((bn + kBCG - 1) / kBCG, kBRows), dim3(512), 0, st, U, pos, A, out,
+                       argmax, dout, scene_off, S, jq, bn, dAp, grid, part);
+  SGG_RETURN_LAUNCH(name);
+}
+
+extern "C" int sgg_pool_bwd_bn(const float* U, const float* pos, const float* A, const float* W2, const float* out,
+                               const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
+                               int max_n, float* dU, float* part, size_t part_floats, void* stream) {
+  return bwd_bn("sgg_pool_bwd_bn", U, pos, A, W2, out, argmax, dout, scene_off, S, B, bn, max_n, dU, part, part_floats,
+                nullptr, stream);
+}
+
+extern "C" int sgg_pool_bwd_bn_drop(const float* U, const float* pos, const float* A, const float* W2,
+                                    const float* out, const int32_t* argmax, const float* dout,
+                                    const int32_t* scene_off, int S, int B, int bn, int max_n, float* dU, float* part,
+                                    size_t part_floats, float p, unsigned long long seed, unsigned offset,
+                                    const unsigned long long* rng_dev, void* stream) {
+  DropArgs d;
+  if (!pool_drop_args("sgg_pool_bwd_bn_drop", p, seed, offset, rng_dev, &d)) return SGG_E_ARG;
+  return bwd_bn("sgg_pool_bwd_bn_drop", U, pos, A, W2, out, argmax, dout, scene_off, S, B, bn, max_n, dU, part,
+                part_floats, &d, stream);
 }

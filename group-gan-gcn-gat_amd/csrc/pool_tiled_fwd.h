@@ -2,6 +2,7 @@
 #pragma once
 #include "sgg_common.h"
 #include "pool_common.h"
+#include "pool_drop.h"
 
 namespace sgg {
 
@@ -26,12 +27,18 @@ constexpr int kWideWaves = 4;
 // everything below a compile-time constant) and pool_fwd_bn_kernel (pool_bn.hip; RT = true, BN = 64: the
 // column tile [cb, cb + ncol) of a W2 / b2 / out / argmax with the runtime row stride bn_rt -- columns
 // >= ncol of the tile have their W2 rows staged as 0 and are neither max-ed nor stored).
-template <int BN, int GPW, bool RT>
+// DROP (pool_fwd_bn_drop_kernel): the hidden value is m1 * relu(..), the epilogue value m2 * relu(..), m the
+// scaled masks of pool_drop.h -- one Philox call per group and four k-steps for m1 (the lane's hidden units
+// k0 + 16 q + 4 s + kq, s = 0..3, are the call's four words), one per output element for m2.  Neither mask
+// sees cb, the j-tile or the pass: every column tile recomputes the same hidden mask.
+template <int BN, int GPW, bool RT, bool DROP = false>
 __device__ __forceinline__ void pool_fwd_tiled_body(
     const float* __restrict__ U, const float* __restrict__ pos, const float* __restrict__ A,
     const float* __restrict__ W2 /* stride x 512 */, const float* __restrict__ b2,
     const int32_t* __restrict__ scene_off, const int4* __restrict__ chunks, int nch, float* __restrict__ out,
-    int32_t* __restrict__ argmax, int cb_rt, int bn_rt) {
+    int32_t* __restrict__ argmax, int cb_rt, int bn_rt, const DropArgs& drop = DropArgs{}) {
+  PoolDropKey dk{};
+  if constexpr (DROP) dk = pool_drop_key(drop);
   const int cb = RT ? cb_rt : 0;                       // first column of the tile
   const int stride = RT ? bn_rt : BN;                  // row stride of W2 / out / argmax, length of b2
   const int ncol = RT ? min(BN, bn_rt - cb_rt) : BN;   // live columns of the tile
@@ -125,12 +132,17 @@ __device__ __forceinline__ void pool_fwd_tiled_body(
         int uoff[GPW];
         float rx[GPW], ry[GPW];
         floatx4 acc[GPW][NT];
+        uint32_t di[GPW], dj[GPW];   // DROP: the lane's pair (global i, scene-local j << 8 | kq) of each group
 #pragma unroll
         for (int g = 0; g < GPW; ++g) {
           const int p = pa * P + (wave * GPW + g) * 16 + c16;
           int il = 0, jl = 0;
           if (p < npairs) { il = p / nj; jl = p - il * nj; }
           uoff[g] = jl * kWKTP + kq;
+          if constexpr (DROP) {
+            di[g] = (uint32_t)(o + i0 + il);
+            dj[g] = ((uint32_t)(jb + jl) << 8) | (uint32_t)kq;
+          }
           const float2 pj = ps[jb + jl], pi = ps[i0 + il];
           rx[g] = p < npairs ? pj.x - pi.x : 0.f;
           ry[g] = p < npairs ? pj.y - pi.y : 0.f;
@@ -149,6 +161,40 @@ __device__ __forceinline__ void pool_fwd_tiled_body(
           a = *reinterpret_cast<const float2*>(As + 2 * kq);
 #pragma unroll
           for (int g = 0; g < GPW; ++g) u[g] = Us[uoff[g]];
+          if constexpr (DROP) {
+            // the k-steps below, four at a time under one mask call per group: its words 0..3 are the lane's
+            // hidden units k0 + 16 q4 + 4 sq + kq
+            for (int q4 = 0; q4 < kWKT / 16; ++q4) {
+              Philox4 x[GPW];
+#pragma unroll
+              for (int g = 0; g < GPW; ++g)
+                x[g] = philox4x32_10(di[g], dj[g] | (uint32_t)(((k0 >> 4) + q4) << 2),
+                                     (uint32_t)SGG_POOL_DROP_SITE_HIDDEN << 8, dk.c3, dk.k0, dk.k1);
+#pragma unroll
+              for (int sq = 0; sq < 4; ++sq) {
+                const int s4 = 4 * q4 + sq;
+                float h[GPW], bc[NT];
+#pragma unroll
+                for (int g = 0; g < GPW; ++g)
+                  h[g] = __fmul_rn(fmaxf(fmaf(a.y, ry[g], fmaf(a.x, rx[g], u[g])), 0.f), pool_drop_mul(dk, x[g].w[sq]));
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bc[t] = b[t];
+                if (s4 + 1 < kWKT / 4) {
+                  const int kn = 4 * (s4 + 1);
+#pragma unroll
+                  for (int t = 0; t < NT; ++t) b[t] = W2s[(kn + kq) * BNP + 16 * t + c16];
+                  a = *reinterpret_cast<const float2*>(As + 2 * (kn + kq));
+#pragma unroll
+                  for (int g = 0; g < GPW; ++g) u[g] = Us[uoff[g] + kn];
+                }
+#pragma unroll
+                for (int g = 0; g < GPW; ++g)
+#pragma unroll
+                  for (int t = 0; t < NT; ++t)
+                    acc[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(h[g], bc[t], acc[g][t], 0, 0, 0);
+              }
+            }
+          } else {
 #pragma unroll 2
           for (int s4 = 0; s4 < kWKT / 4; ++s4) {
             float h[GPW], bc[NT];
@@ -170,10 +216,30 @@ __device__ __forceinline__ void pool_fwd_tiled_body(
               for (int t = 0; t < NT; ++t)
                 acc[g][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(h[g], bc[t], acc[g][t], 0, 0, 0);
           }
+          }
           __syncthreads();  // tile consumed
           if (!last_k || more) {
             store_tile();
             __syncthreads();
+          }
+        }
+
+        // DROP: the output mask's keep bits of the lane's (g, r, t) elements, by a loop that stays rolled (the
+        // epilogue below must unroll for acc's static indices; with the mask calls inside it does not)
+        unsigned long long kb = 0ull;
+        if constexpr (DROP) {
+          static_assert(4 * GPW * NT <= 64, "keep bits of one pass in 64 bits");
+#pragma unroll 1
+          for (int gr = 0; gr < 4 * GPW; ++gr) {
+            const int p = pa * P + (wave * GPW + (gr >> 2)) * 16 + kq * 4 + (gr & 3);
+            if (p < npairs) {
+              const int il = p / nj, j = jb + (p - il * nj);
+#pragma unroll
+              for (int t = 0; t < NT; ++t)
+                kb |= (unsigned long long)pool_drop_keep(dk, SGG_POOL_DROP_SITE_OUT, (uint32_t)(o + i0 + il), (uint32_t)j,
+                                                         (uint32_t)(cb + 16 * t + c16))
+                      << (gr * NT + t);
+            }
           }
         }
 
@@ -193,6 +259,7 @@ __device__ __forceinline__ void pool_fwd_tiled_body(
                 if (cc < ncol) {
                   float v = acc[g][t][r] + bv[t];
                   v = v > 0.f ? v : 0.f;
+                  if constexpr (DROP) v = (kb >> ((4 * g + r) * NT + t)) & 1ull ? __fmul_rn(v, dk.scale) : 0.f;
                   atomicMax(&keys[il * BN + cc], ((unsigned long long)__float_as_uint(v) << 32) | jkey);
                 }
               }

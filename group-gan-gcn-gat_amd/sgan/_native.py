@@ -287,6 +287,9 @@ SIGNATURES = {
     "sgg_dec_step_fwd": (_i, [ctypes.POINTER(DecStep), _p]),
     "sgg_dec_step_bwd": (_i, [ctypes.POINTER(DecStepBwd), _p]),
     "sgg_pool_dpos": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "sgg_pool_fwd_bn_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _f, _u64, _u, _p, _p]),
+    "sgg_pool_bwd_bn_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _f, _u64, _u, _p, _p]),
+    "sgg_pool_dpos_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _f, _u64, _u, _p, _p]),
 }
 
 VAL_SLOTS = 11   # SGG_VAL_SLOTS

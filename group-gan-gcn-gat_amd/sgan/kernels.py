@@ -302,7 +302,7 @@ def lstm_fold_spec(lstm, emb):
 
 
 def pool_fold_spec(pool):
-    l1, E = pool.mlp_pre_pool[0], pool.embedding_dim
+    l1, E = pool_linears(pool)[0], pool.embedding_dim
     return (l1.weight[:, :E], pool.spatial_embedding.weight, pool.spatial_embedding.bias, l1.bias, None)
 
 
@@ -1583,10 +1583,163 @@ def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, dh_in
     return out
 
 
+class _PoolDrop(torch.autograd.Function):
+    """_Pool for a pooling net built with dropout > 0, in training: the two
+    nn.Dropout of mlp_pre_pool as the stateless masks of include/sgg.h
+    "Pooling dropout masks" (drop = (p, seed, offset)), on the column-tiled
+    family's dropout form at EVERY width (sgg_pool_fwd_bn_drop /
+    sgg_pool_bwd_bn_drop) -- like every launch of that family fp32 in either
+    precision, never paired, no dh handoff.  Same arguments, outputs and
+    parameter gradients as _Pool."""
+
+    @staticmethod
+    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop):
+        lib = _lib()
+        p, seed, offset = float(drop[0]), int(drop[1]) & 0xFFFFFFFFFFFFFFFF, int(drop[2]) & 0xFFFFFFFF
+        if not 0.0 <= p < 1.0:
+            raise ValueError("pooling dropout p=%r outside [0, 1)" % p)
+        pool_is_wide(scenes)    # a scene above the tiled kernels' bound: ValueError before any launch
+        h = _rows(h, "h")
+        pos = _req(pos, "pos").contiguous()
+        B, Hd = h.shape
+        E = We.shape[0]
+        bn = W2.shape[0]
+        assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
+        assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
+        if bn > POOL_BN_MAX:
+            raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
+                                "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
+        # (a fixed-capacity batch refuses here, naming dropout, before the fold and the U product)
+        chunks, nchunks, max_rows, gpw = scenes.pool_plan(bn, family_bn=True, dropout=True)[:4]
+        W1, W2, b2 = W1.contiguous(), W2.contiguous(), b2.contiguous()
+        A, c = fold_fwd(W1[:, :E], We, be, b1)
+        U = xw_raw(h, W1[:, E:], c, trans_w=True)             # B x 512
+        out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
+        am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
+
+        def launch():
+            N.check(lib.sgg_pool_fwd_bn_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
+                                             N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
+                                             scenes.max_n, N.ptr(out), N.ptr(am), p, seed, offset, None,
+                                             N.stream_ptr()), "sgg_pool_fwd_bn_drop")
+        rider = _PRIDER[0]
+        if rider is not None:
+            rider.flush()    # a held forward goes out first, on its own
+        launch()
+        if timer.active:
+            nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn
+            timer.add("sgg::pool_fwd_bn_drop_kernel", (scenes.S, B), _pool_flops_bn(scenes, bn), nb + _pool_wbytes(bn),
+                      launch)
+        ctx.scenes, ctx.E, ctx.link, ctx.drop = scenes, E, link, (p, seed, offset)
+        ctx.save_for_backward(h, pos, W1, We, be, A, W2, U, out, am)
+        ctx.mark_non_differentiable(am)
+        ctx.set_materialize_grads(False)
+        return out, am
+
+    @staticmethod
+    def backward(ctx, dout, _dam):
+        lib = _lib()
+        h, pos, W1, We, be, A, W2, U, out, am = ctx.saved_tensors
+        sc, E = ctx.scenes, ctx.E
+        p, seed, offset = ctx.drop
+        B, bn = out.shape
+        H = h.shape[1]
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        wgrad = any(need[2:8])       # False: weights frozen, input gradient only
+        P = bn * 512 + 1024 + bn
+        dU = torch.empty(B, 512, device=h.device, dtype=torch.float32)
+        rows = lib.sgg_pool_bwd_bn_grid(sc.S, bn, sc.max_n)
+        nws = lib.sgg_pool_bwd_bn_ws_floats(sc.S, B, bn, sc.max_n)
+        if rows < 0 or nws < 0:
+            N.check(-1, "sgg_pool_bwd_bn_ws_floats")
+        part = torch.empty(nws, device=h.device, dtype=torch.float32) if wgrad else None
+
+        def launch():
+            N.check(lib.sgg_pool_bwd_bn_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                             N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
+                                             N.ptr(part), nws if wgrad else 0, p, seed, offset, None,
+                                             N.stream_ptr()), "sgg_pool_bwd_bn_drop")
+        launch()
+        if timer.active:
+            nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * nws if wgrad else 0.0)
+            name = "sgg::pool_bwd_bn_du_drop_kernel<%s>%s" % (("true", " + sgg::pool_bwd_bn_dw_drop_kernel") if wgrad
+                                                             else ("false", ""))
+            timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
+        dh = None
+        if need[0]:
+            # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
+            base = ctx.link.take() if ctx.link is not None else None
+            dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
+        if not wgrad:
+            return dh, None, None, None, None, None, None, None, None, None, None
+        # as _Pool.backward: the slab's row sums, dW1h = dU^T h, dc, the fold backward of (dA, dc)
+        ws, splits = xtw_partial(h, dU, colsum=True)
+        dW1 = torch.empty_like(W1)
+        dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
+        db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
+        dc = torch.empty(512, device=h.device, dtype=torch.float32)
+        gf = GradFinish()
+        gf.rowsum(part, rows, P, 0, bn * 512, dW2)
+        gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
+        gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
+        _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
+                              dW=dW1[:, :E])
+        gf.run()
+        return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None
+
+
+class _PoolDropPos(torch.autograd.Function):
+    """_PoolDrop with the gradient of the positions (sgg_pool_dpos_drop), as
+    _PoolPos is to _Pool: the per-step rollout pools at predicted positions."""
+
+    @staticmethod
+    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop):
+        return _PoolDrop.forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop)
+
+    @staticmethod
+    def backward(ctx, dout, _dam):
+        # (one pooling net at every step: its parameter gradients are written now, see _PoolPos.backward)
+        prev, _DEFER[0] = _DEFER[0], 0
+        try:
+            grads = list(_PoolDrop.backward(ctx, dout, _dam))
+        finally:
+            _DEFER[0] = prev
+        if ctx.needs_input_grad[1]:
+            _h, pos, _W1, _We, _be, A, W2, U, out, am = ctx.saved_tensors
+            sc = ctx.scenes
+            p, seed, offset = ctx.drop
+            B, bn = out.shape
+            dout = dout.contiguous()
+            dpos = torch.empty(B, 2, device=pos.device, dtype=torch.float32)
+            N.check(_lib().sgg_pool_dpos_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                              N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, N.ptr(dpos), p, seed,
+                                              offset, None, N.stream_ptr()), "sgg_pool_dpos_drop")
+            grads[1] = dpos
+        return tuple(grads)
+
+
+def social_pool_drop(h, pos, W1, We, be, b1, W2, b2, scenes, drop, link=None, pos_grad=False):
+    """social_pool / social_pool_pos of a pooling net with dropout > 0 in
+    training; drop = (p, seed, offset), one (seed, offset) per forward."""
+    op = _PoolDropPos if pos_grad else _PoolDrop
+    out, _ = op.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, drop)
+    return out
+
+
+def pool_linears(pool):
+    """The two Linear layers of a PoolHiddenNet's mlp_pre_pool, found by type:
+    built with dropout > 0 the Sequential is [Linear, ReLU, Dropout, Linear,
+    ReLU, Dropout], so the second one is [3], not [2]."""
+    ls = [m for m in pool.mlp_pre_pool if isinstance(m, torch.nn.Linear)]
+    assert len(ls) == 2, "PoolHiddenNet.mlp_pre_pool: %d Linear layers" % len(ls)
+    return ls[0], ls[1]
+
+
 def pool_u_spec(pool):
     """(Wu, cu) of a PoolHiddenNet for the encoder's projection epilogue:
     Wu = W1[:, E:] (in place), cu = W1[:, :E] be + b1 (the cached fold)."""
-    l1, E = pool.mlp_pre_pool[0], pool.embedding_dim
+    l1, E = pool_linears(pool)[0], pool.embedding_dim
     _, c = fold_fwd(l1.weight[:, :E], pool.spatial_embedding.weight, pool.spatial_embedding.bias, l1.bias)
     return l1.weight[:, E:], c
 
@@ -1634,6 +1787,34 @@ def dropout_keep_host(p, seed, offset, site, head, rows, cols):
     w = np.stack(np.broadcast_arrays(*w), 0)                 # word, row, col
     sel = np.broadcast_to((rows & np.uint64(3)).astype(np.int64), w.shape[1:])
     return np.take_along_axis(w, sel[None], 0)[0] >= thr
+
+
+POOL_DROP_SITE_HIDDEN = 16   # SGG_POOL_DROP_SITE_HIDDEN: after the pooling net's first ReLU (col = hidden unit)
+POOL_DROP_SITE_OUT = 17      # SGG_POOL_DROP_SITE_OUT: after its second ReLU (col = output column)
+
+
+def pool_dropout_keep_host(p, seed, offset, site, i_rows, j_local, cols):
+    """The pooling kernels' dropout mask on the host (include/sgg.h "Pooling
+    dropout masks", csrc/pool_drop.h): the boolean keep decisions of the
+    elements i_rows x j_local x cols -- i_rows: global rows of the pooled
+    peds, j_local: scene-local indices of the other peds, cols: hidden units
+    (site POOL_DROP_SITE_HIDDEN) or output columns (POOL_DROP_SITE_OUT) -- as a
+    (len(i_rows), len(j_local), len(cols)) array."""
+    import numpy as np
+    thr, _ = dropout_thr_scale_host(p)
+    i = np.asarray(i_rows, dtype=np.uint64).reshape(-1, 1, 1)
+    j = np.asarray(j_local, dtype=np.uint64).reshape(1, -1, 1)
+    c = np.asarray(cols, dtype=np.uint64).reshape(1, 1, -1)
+    if site >= 1 << 24 or (j.size and int(j.max()) >= 1 << 24) or (c.size and int(c.max()) >= 1024):
+        raise ValueError("pooling dropout: site %d / j / col outside the counter's fields" % site)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    # one call per (i, j, col >> 4, col & 3): its four words are columns col, col + 4, col + 8, col + 12
+    call, inv = np.unique((((c >> np.uint64(4)) << np.uint64(2)) | (c & np.uint64(3))).reshape(-1), return_inverse=True)
+    w = philox4x32_10_host((i, (j << np.uint64(8)) | call.reshape(1, 1, -1), site << 8, int(offset) & 0xFFFFFFFF),
+                           (seed & 0xFFFFFFFF, seed >> 32))
+    w = np.stack(np.broadcast_arrays(*w), 0)                 # word, i, j, call
+    word = ((c.reshape(-1) >> np.uint64(2)) & np.uint64(3)).astype(np.int64)
+    return w[word, :, :, inv.reshape(-1)].transpose(1, 2, 0) >= thr
 
 
 class DropoutRng:

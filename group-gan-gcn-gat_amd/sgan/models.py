@@ -218,7 +218,7 @@ class Decoder(nn.Module):
         K.prefold([K.lstm_fold_spec(self.decoder, self.spatial_embedding), K.pool_fold_spec(pool)])
         ro = K.dec_rollout(T, B, self.decoder, self.spatial_embedding, self.hidden2pos, self.mlp,
                            K.pool_u_spec(pool), fuse_mlp, (h, c, last_pos_rel, last_pos), h.device)
-        l1, l2, emb = pool.mlp_pre_pool[0], pool.mlp_pre_pool[2], pool.spatial_embedding
+        (l1, l2), emb = K.pool_linears(pool), pool.spatial_embedding
         rel, pos, pool_h, rels = last_pos_rel, last_pos, None, []
         for t in range(T):
             if pool_h is not None and not fuse_mlp:
@@ -243,7 +243,11 @@ class PoolHiddenNet(nn.Module):
     """Pooling module as proposed in Social-GAN.  The pair MLP runs fused in
     sgg_pool_fwd; the spatial embedding is folded into the first layer
     (A = W1e We, c = W1e be + b1, sgg_fold_fwd) inside the autograd op, which
-    returns the raw parameters' gradients."""
+    returns the raw parameters' gradients.  Built with dropout > 0 (the two
+    nn.Dropout of mlp_pre_pool): train() runs the column-tiled family's
+    dropout form with the stateless masks (K.social_pool_drop, one (seed,
+    offset) of K.DROPOUT_RNG per forward), eval() the kernels of a dropout=0
+    net, bitwise."""
 
     def __init__(self, embedding_dim=64, h_dim=64, mlp_dim=1024, bottleneck_dim=1024, activation="relu",
                  batch_norm=True, dropout=0.0):
@@ -265,15 +269,22 @@ class PoolHiddenNet(nn.Module):
         """U (optional): h W1[:, E:]^T + c already computed by the encoder
         kernel's epilogue (K.pool_u_spec).  pos_grad: end_pos is a prediction
         (the per-step rollout), so the backward returns its gradient too."""
-        if not self.fused_ok():
+        if self.batch_norm or self.activation != "relu":
             raise NotImplementedError("the fused pooling kernel implements the reference configs "
-                                      "(batch_norm=0, relu, dropout=0)")
+                                      "(batch_norm=0, relu)")
         if self.bottleneck_dim > K.POOL_BN_MAX:    # refused before any launch
             raise K.N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
                                 "(SGG_POOL_BN_MAX)" % (self.bottleneck_dim, K.POOL_BN_MAX))
         sc = _scenes(seq_start_end, end_pos.device, scenes)
-        l1, l2 = self.mlp_pre_pool[0], self.mlp_pre_pool[2]
+        l1, l2 = K.pool_linears(self)
         emb = self.spatial_embedding
+        if self.dropout > 0 and self.training:
+            # the dropout form: never on U from an encoder epilogue, no dh handoff (fused_ok() is False, so
+            # no caller passes either)
+            seed, offset = K.DROPOUT_RNG.next()
+            return K.social_pool_drop(h_states.reshape(-1, self.h_dim), end_pos, l1.weight, emb.weight, emb.bias,
+                                      l1.bias, l2.weight, l2.bias, sc, (self.dropout, seed, offset), link=link,
+                                      pos_grad=pos_grad)
         if pos_grad:
             return K.social_pool_pos(h_states.reshape(-1, self.h_dim), end_pos, l1.weight, emb.weight, emb.bias,
                                      l1.bias, l2.weight, l2.bias, sc, U=U)

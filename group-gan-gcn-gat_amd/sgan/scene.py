@@ -78,7 +78,7 @@ class SceneIndex:
     POOL_WIDE_TARGET_CHUNKS = int(__import__("os").environ.get("SGG_POOL_WIDE_TARGET_CHUNKS", "2048"))
     POOL_MAX_GPW = int(__import__("os").environ.get("SGG_POOL_MAX_GPW", "0"))
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False, family_bn=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False, family_bn=False, dropout=False):
         """Device chunk table for sgg_pool_fwd (built on the host by
         sgg_pool_plan, cached per bottleneck width); bf16: the table of
         sgg_pool_fwd_bf16 (sgg_pool_plan_bf16: big chunks, one per CU);
@@ -86,7 +86,9 @@ class SceneIndex:
         up to SGG_POOL_WIDE_MAX_PEDS peds, fp32 only); family_bn: the table of
         sgg_pool_fwd_bn (sgg_pool_plan_bn: any width up to SGG_POOL_BN_MAX,
         every scene size, fp32 only -- the row chunks are shared by the
-        launch's column tiles, so the target is divided by their number)."""
+        launch's column tiles, so the target is divided by their number);
+        dropout: the caller's statement that the launch is the family's
+        dropout form (the same table; a fixed-capacity batch refuses it)."""
         if family_bn:
             target_chunks = target_chunks or max(8, self.POOL_WIDE_TARGET_CHUNKS // ((bn + 63) // 64))
         target_chunks = target_chunks or (self.POOL_WIDE_TARGET_CHUNKS if wide else
@@ -282,11 +284,16 @@ class PaddedScenes(SceneIndex):
         """Offset of plan k: [chunk count, 0, 0, 0 | pool_cap x (scene, i0, i1, gpw)]."""
         return self._plan_base + (4 + 4 * self.pool_cap) * k
 
-    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False, family_bn=False):
+    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False, family_bn=False, dropout=False):
         """(chunk table, grid basis, max rows, gpw, device chunk count): the
         table holds up to pool_cap chunks; the kernels walk the device count,
         the grid is sized by the chunk count of the batch that registered the
         plan (the capture's)."""
+        if dropout:
+            # the dropout form lives in the column-tiled family, which has no fixed-capacity plan
+            raise NotImplementedError("PaddedScenes: a pooling net with dropout > 0 in training is not supported "
+                                      "(the dropout form of the pooling kernels has no padded-batch plan); "
+                                      "use SceneIndex batches (scripts/train.py --dropout)")
         if family_bn or bn not in POOL_BUILT_BN:
             # the padded-batch contract is pinned for the resident kernels only: refused before any launch
             raise NotImplementedError("PaddedScenes: bottleneck_dim=%d is not one of the resident pooling kernels' "
@@ -423,9 +430,9 @@ class _PaddedRepeat(SceneIndex):
     def ped_scene_long(self):
         raise NotImplementedError("PaddedScenes.repeat: no ped-scene map")
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False, family_bn=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, family_bn=False, dropout=False):
         # (the fixed-capacity plan serves both precisions: the bf16 kernel takes any chunk table)
-        return self.parent.pool_plan(bn, target_chunks, rep=self.k, family_bn=family_bn)
+        return self.parent.pool_plan(bn, target_chunks, rep=self.k, family_bn=family_bn, dropout=dropout)
 
     def groups(self, labels):
         raise NotImplementedError("PaddedScenes: the per-op group index is not captured")

@@ -256,6 +256,14 @@ class GanTrainer:
             raise NotImplementedError("GanTrainer: a generator with dropout1=%g is not supported (the shared G "
                                       "context would give all best_k samples one dropout mask); drive the modules "
                                       "with the reference's own step functions (scripts/train.py --dropout1)" % p1)
+        pd = [m.dropout for m in (getattr(G, "pool_net", None), getattr(getattr(G, "decoder", None), "pool_net", None))
+              if m is not None and getattr(m, "dropout", 0) and m.dropout > 0]
+        if pd:
+            # the same reason: one pooling forward of the shared context would serve all best-of-k samples
+            raise NotImplementedError("GanTrainer: a generator whose pooling net has dropout=%g is not supported (the "
+                                      "shared G context would give all best_k samples one dropout mask); drive the "
+                                      "modules with the reference's own step functions (scripts/train.py --dropout)"
+                                      % pd[0])
         # Adam over ALL of G's parameters, as train.py:238 builds it, so the
         # optimizer state (and its index order) matches reference checkpoints;
         # the unused graph module gets no gradient and Adam skips it

@@ -1406,6 +1406,60 @@ int sgg_pool_dpos(const float* U, const float* pos, const float* A, const float*
                   const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
                   float* dpos, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Pooling dropout masks: the pooling net built with dropout > 0
+ * (mlp_pre_pool = Linear, ReLU, Dropout, Linear, ReLU, Dropout; reference
+ * models.py:7-20, :521-541) in training.  Two sites, both masks over the
+ * reference's pair rows i_local * n + j_local:
+ *   SGG_POOL_DROP_SITE_HIDDEN  after the first ReLU: element (i, j, k), k the
+ *                              hidden unit 0..511;
+ *   SGG_POOL_DROP_SITE_OUT     after the second ReLU, before the max over j:
+ *                              element (i, j, c), c the output column 0..bn-1.
+ * i is the GLOBAL row of the pooled ped (scene_off[s] + i_local), j the
+ * scene-local index of the other ped, col = k or c.  Generator, key, keep rule
+ * and scale are those of "Dropout masks" above; the counter is
+ *   (i, (j << 8) | ((col >> 4) << 2) | (col & 3), site << 8, offset)
+ * and the element uses output word (col >> 2) & 3, so the four words of one
+ * call cover columns col, col + 4, col + 8, col + 12 (the hidden units one
+ * lane of the forward owns over four k-steps).  The mask is a pure function of
+ * (seed, offset, site, i, j, col): it never depends on the column tile, the
+ * j tile, the pass, the grid or the instantiation, so every column tile of the
+ * forward recomputes the same hidden mask and the backward regenerates it.
+ * sgan.kernels.pool_dropout_keep_host restates it in numpy.
+ *
+ * sgg_pool_fwd_bn_drop: sgg_pool_fwd_bn (every bn in 1 .. SGG_POOL_BN_MAX,
+ * scenes of 1 .. SGG_POOL_WIDE_MAX_PEDS peds, the plan of sgg_pool_plan_bn)
+ * with hidden = m1 relu(U_j + A (pos_j - pos_i)) and out[i, c] = max_j m2
+ * relu(W2 hidden + b2), m the scaled masks; argmax as there (the first j of
+ * the maximum; where out == 0 it carries no gradient).
+ * sgg_pool_bwd_bn_drop: sgg_pool_bwd_bn (same workspace contract:
+ * sgg_pool_bwd_bn_grid, sgg_pool_bwd_bn_ws_floats, part == NULL for frozen
+ * weights, same order of every sum) with the output gate dout * scale where
+ * out > 0 (which implies the output mask kept the pair: that mask is not
+ * regenerated) and m1 on the recomputed hidden units of the selected pairs.
+ * sgg_pool_dpos_drop: sgg_pool_dpos with the same two factors (bn up to
+ * SGG_POOL_BN_MAX).
+ * p, seed, offset, rng_dev as the sgg_gat_*_drop entry points take them; p
+ * outside [0, 1) and every bad argument of the plain entry points is SGG_E_ARG
+ * before any launch.  At p = 0 out / argmax are bitwise sgg_pool_fwd_bn's and
+ * dU is bitwise sgg_pool_bwd_bn's. */
+#define SGG_POOL_DROP_SITE_HIDDEN 16
+#define SGG_POOL_DROP_SITE_OUT 17
+int sgg_pool_fwd_bn_drop(const float* U, const float* pos, const float* A, const float* W2,
+                         const float* b2, const int32_t* scene_off, const int32_t* chunks, int nchunks,
+                         int max_rows, int gpw, int B, int bn, int max_n, float* out, int32_t* argmax,
+                         float p, unsigned long long seed, unsigned offset,
+                         const unsigned long long* rng_dev, void* stream);
+int sgg_pool_bwd_bn_drop(const float* U, const float* pos, const float* A, const float* W2,
+                         const float* out, const int32_t* argmax, const float* dout,
+                         const int32_t* scene_off, int S, int B, int bn, int max_n,
+                         float* dU, float* part, size_t part_floats, float p, unsigned long long seed,
+                         unsigned offset, const unsigned long long* rng_dev, void* stream);
+int sgg_pool_dpos_drop(const float* U, const float* pos, const float* A, const float* W2, const float* out,
+                       const int32_t* argmax, const float* dout, const int32_t* scene_off, int S, int B, int bn,
+                       float* dpos, float p, unsigned long long seed, unsigned offset,
+                       const unsigned long long* rng_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

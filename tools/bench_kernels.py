@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|poolbn|gatwide|gatdrop|...]
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|poolbn|pooldrop|gatwide|gatdrop|...]
 validate [a|b]: wall time of one check_accuracy pass, three routes; valkernel: sgg_val_metrics alone."""
 import os
 import sys
@@ -151,6 +151,49 @@ def poolbn(S, n, bn, reps=20):
               "bwd %8.1f us  bwd(dU only) %8.1f us  ws %.1f MB" % (
                   name, S, n, bn, tiles, nchunks, max_rows, uf, flops / uf / 1e6, uf * 1e3 / (S * n * n), ub, ub0,
                   part.numel() * 4 / 1e6), flush=True)
+
+
+def pooldrop(S, n, bn, p=0.5, reps=20):
+    """The dropout form of the column-tiled pooling kernels (sgg_pool_fwd_bn_drop
+    / sgg_pool_bwd_bn_drop at probability p) beside the plain launches
+    (sgg_pool_fwd_bn / sgg_pool_bwd_bn) on the same operands: forward, backward
+    with weight gradients, dU-only backward; each backward on its own
+    forward's out / argmax.  Device events around reps launches after 3
+    warm-ups (timeit)."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B = S * n
+    sc = SceneIndex(np.arange(0, B + 1, n), dev)
+    U = torch.randn(B, 512, device=dev) * 0.3
+    pos = torch.rand(B, 2, device=dev) * 15
+    A = torch.randn(512, 2, device=dev) * 0.3
+    W2 = torch.randn(bn, 512, device=dev) * 0.05
+    b2 = torch.randn(bn, device=dev) * 0.1
+    dout = torch.randn(B, bn, device=dev)
+    lib = N.load()
+    out = torch.empty(B, bn, device=dev)
+    am = torch.empty(B, bn, device=dev, dtype=torch.int32)
+    dU = torch.empty(B, 512, device=dev)
+    chunks, nchunks, max_rows, g = sc.pool_plan(bn, family_bn=True)
+    part = torch.empty(lib.sgg_pool_bwd_bn_ws_floats(S, B, bn, n), device=dev)
+    fargs = (N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(sc.scene_off), N.ptr(chunks), nchunks,
+             max_rows, g, B, bn, sc.max_n, N.ptr(out), N.ptr(am))
+    bargs = (N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout), N.ptr(sc.scene_off), S, B,
+             bn, sc.max_n, N.ptr(dU))
+    drop = (p, 12345, 0, None)
+    res = {}
+    for name, extra, ffn, bfn in (("plain", (), lib.sgg_pool_fwd_bn, lib.sgg_pool_bwd_bn),
+                                  ("drop", drop, lib.sgg_pool_fwd_bn_drop, lib.sgg_pool_bwd_bn_drop)):
+        fwd = lambda: N.check(ffn(*fargs, *extra, N.stream_ptr()), "fwd")
+        bwd = lambda: N.check(bfn(*bargs, N.ptr(part), part.numel(), *extra, N.stream_ptr()), "bwd")
+        bwd0 = lambda: N.check(bfn(*bargs, None, 0, *extra, N.stream_ptr()), "bwd")
+        res[name] = (timeit(fwd, reps), timeit(bwd0, reps), timeit(bwd, reps))
+    for name in ("plain", "drop"):
+        uf, ub0, ub = res[name]
+        print("pool %-5s S=%3d n=%4d bn=%4d p=%.2f  fwd %8.1f us  bwd(dU only) %8.1f us  bwd %8.1f us" % (
+            name, S, n, bn, p if name == "drop" else 0.0, uf, ub0, ub), flush=True)
+    print("pool ratio S=%3d n=%4d bn=%4d        fwd %8.2f x   bwd(dU only) %8.2f x   bwd %8.2f x" % (
+        (S, n, bn) + tuple(d / q for d, q in zip(res["drop"], res["plain"]))), flush=True)
 
 
 def gatwide(S, n, heads, F, reps=20):
@@ -474,6 +517,10 @@ if __name__ == "__main__":
         for (S, n) in ((64, 20), (512, 20)):
             for bn in (64, 128, 1024):
                 poolbn(S, n, bn)
+        sys.exit(0)
+    if what == "pooldrop":   # what the two dropout masks cost inside the column-tiled pooling kernels
+        for bn in (8, 64, 1024):
+            pooldrop(64, 20, bn)
         sys.exit(0)
     if what == "gatwide":   # the tiled attention kernels above 128 nodes, next to the resident ones at 128
         for (S, n) in ((32, 128), (8, 256), (1, 1024)):
