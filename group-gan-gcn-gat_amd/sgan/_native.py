@@ -290,6 +290,12 @@ SIGNATURES = {
     "sgg_pool_fwd_bn_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _f, _u64, _u, _p, _p]),
     "sgg_pool_bwd_bn_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _f, _u64, _u, _p, _p]),
     "sgg_pool_dpos_drop": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _f, _u64, _u, _p, _p]),
+    "sgg_pool_norm_fwd": (_i, [_p] * 10 + [_i] * 5 + [_f, _f] + [_p] * 9),
+    "sgg_pool_norm_running": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p]),
+    "sgg_pool_norm_bwd_rows": (_i, [_i]),
+    "sgg_pool_norm_bwd_ws_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "sgg_pool_norm_bwd_slab_offset": (ctypes.c_longlong, [_i, _i]),
+    "sgg_pool_norm_bwd": (_i, [_p] * 18 + [_i] * 5 + [_f, _f, _i, _p, _p, _p, _sz, _p]),
 }
 
 VAL_SLOTS = 11   # SGG_VAL_SLOTS

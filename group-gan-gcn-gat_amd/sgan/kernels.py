@@ -1727,6 +1727,226 @@ def social_pool_drop(h, pos, W1, We, be, b1, W2, b2, scenes, drop, link=None, po
     return out
 
 
+POOL_NORM_MAX_PEDS = 256   # SGG_POOL_NORM_MAX_PEDS: scene bound of the batch-norm pooling kernels in train()
+
+
+def pool_norms(pool):
+    """The two BatchNorm1d of a PoolHiddenNet built with batch_norm=1."""
+    ns = [m for m in pool.mlp_pre_pool if isinstance(m, torch.nn.BatchNorm1d)]
+    assert len(ns) == 2, "PoolHiddenNet.mlp_pre_pool: %d BatchNorm1d layers" % len(ns)
+    return ns[0], ns[1]
+
+
+def pool_norm_fold(lin, norm):
+    """(Linear, BatchNorm1d in eval()) as one Linear: with s = gamma /
+    sqrt(running_var + eps), W' = diag(s) W and b' = (b - running_mean) s +
+    beta.  Torch ops on the device; autograd reaches the raw parameters."""
+    s = norm.weight / torch.sqrt(norm.running_var + norm.eps)
+    return lin.weight * s[:, None], (lin.bias - norm.running_mean) * s + norm.bias
+
+
+def pool_norm_modules_check(norms):
+    """The BatchNorm1d forms the pooling net takes, in train() and in eval()
+    (without running statistics torch normalises with batch statistics in
+    eval() too, which the fold cannot express): raises before any launch."""
+    for m in norms:
+        if m.momentum is None or not m.track_running_stats or m.running_mean is None:
+            raise NotImplementedError("social pooling with batch_norm: momentum=None (cumulative average) and "
+                                      "track_running_stats=False are not supported by the pooling kernels")
+        if not m.affine:
+            raise NotImplementedError("social pooling with batch_norm: affine=False is not supported")
+
+
+def pool_norm_check(scenes, bn, norms, dropout=0.0):
+    """The refusals of the batch-norm pooling in train(), each before any
+    launch; returns the batch's smallest scene size."""
+    pool_norm_modules_check(norms)
+    if dropout > 0:
+        raise NotImplementedError("social pooling: batch_norm together with dropout > 0 in train() is not supported "
+                                  "(the batch_norm kernels have no dropout form)")
+    if bn > POOL_BN_MAX:
+        raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
+                            "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
+    scenes.pool_plan(bn, batch_norm=True)     # a fixed-capacity batch refuses here, naming batch_norm
+    import numpy as np
+    sizes = np.diff(np.asarray(scenes.host_off))
+    min_n = int(sizes.min()) if sizes.size else 2
+    if min_n < 2:
+        # torch's own refusal of a one-row batch in train() (a one-ped scene has one pair row)
+        raise ValueError("Expected more than 1 value per channel when training, got input size "
+                         "torch.Size([%d, 512]) (social pooling with batch_norm: a scene of %d ped)"
+                         % (min_n * min_n, min_n))
+    if scenes.max_n > POOL_NORM_MAX_PEDS:
+        raise NotImplementedError("social pooling with batch_norm in train(): a scene of %d pedestrians exceeds the "
+                                  "bound of %d per scene (SGG_POOL_NORM_MAX_PEDS)" % (scenes.max_n, POOL_NORM_MAX_PEDS))
+    return min_n
+
+
+class _PoolNorm(torch.autograd.Function):
+    """_Pool for a pooling net built with batch_norm=1, in train(): both
+    BatchNorm1d of mlp_pre_pool on each scene's own n x n pair rows
+    (sgg_pool_norm_fwd / sgg_pool_norm_bwd, include/sgg.h), fp32 in either
+    precision, at every width, never paired, no dh handoff.  The running
+    statistics are updated on the device in scene order
+    (sgg_pool_norm_running).  g1 / t1, g2 / t2: the BatchNorm weights and
+    biases; stats = per layer (eps, momentum, running_mean, running_var,
+    num_batches_tracked).  The three biases in front of a BatchNorm (be, b1,
+    b2) get exact zeros as gradients."""
+
+    @staticmethod
+    def forward(ctx, h, pos, W1, We, be, b1, g1, t1, W2, b2, g2, t2, scenes, link, stats, min_n, want_dpos):
+        lib = _lib()
+        (eps1, mom1, rm1, rv1, nbt1), (eps2, mom2, rm2, rv2, nbt2) = stats
+        h = _rows(h, "h")
+        pos = _req(pos, "pos").contiguous()
+        B, Hd = h.shape
+        E = We.shape[0]
+        bn = W2.shape[0]
+        S = scenes.S
+        assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
+        assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
+        W1, W2, b2 = W1.contiguous(), W2.contiguous(), b2.contiguous()
+        g1, t1, g2, t2 = g1.contiguous(), t1.contiguous(), g2.contiguous(), t2.contiguous()
+        A, c = fold_fwd(W1[:, :E], We, be, b1)
+        U = xw_raw(h, W1[:, E:], c, trans_w=True, prec="fp32")             # B x 512, fp32 in either precision
+        dev, f32 = h.device, torch.float32
+        Un = torch.empty(B, 512, device=dev, dtype=f32)
+        An = torch.empty(S, 1024, device=dev, dtype=f32)
+        mu1 = torch.empty(S, 512, device=dev, dtype=f32)
+        var1 = torch.empty(S, 512, device=dev, dtype=f32)
+        mu2 = torch.empty(S, bn, device=dev, dtype=f32)
+        var2 = torch.empty(S, bn, device=dev, dtype=f32)
+        out = torch.empty(B, bn, device=dev, dtype=f32)
+        am = torch.empty(B, bn, device=dev, dtype=torch.int32)
+
+        def launch():
+            N.check(lib.sgg_pool_norm_fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(g1), N.ptr(t1), N.ptr(W2), N.ptr(b2),
+                                          N.ptr(g2), N.ptr(t2), N.ptr(scenes.scene_off), S, B, bn, min_n,
+                                          scenes.max_n, eps1, eps2, N.ptr(Un), N.ptr(An), N.ptr(mu1), N.ptr(var1),
+                                          N.ptr(mu2), N.ptr(var2), N.ptr(out), N.ptr(am), N.stream_ptr()),
+                    "sgg_pool_norm_fwd")
+        rider = _PRIDER[0]
+        if rider is not None:
+            rider.flush()    # a held forward goes out first, on its own
+        launch()
+        if timer.active:
+            nb = 4.0 * (2 * B * 512 + 2 * B) + 8.0 * B * bn
+            timer.add("sgg::pool_norm_fwd_kernel", (S, B), 2.0 * _pool_flops_bn(scenes, bn), nb + _pool_wbytes(bn),
+                      launch)
+        for mean, var, C, mom, rm, rv, nbt in ((mu1, var1, 512, mom1, rm1, rv1, nbt1),
+                                               (mu2, var2, bn, mom2, rm2, rv2, nbt2)):
+            N.check(lib.sgg_pool_norm_running(N.ptr(mean), N.ptr(var), N.ptr(scenes.scene_off), S, C, mom,
+                                              N.ptr(rm), N.ptr(rv), N.stream_ptr()), "sgg_pool_norm_running")
+            if nbt is not None:
+                nbt.add_(S)
+        ctx.scenes, ctx.E, ctx.link, ctx.eps, ctx.min_n, ctx.want_dpos = scenes, E, link, (eps1, eps2), min_n, want_dpos
+        ctx.save_for_backward(h, pos, W1, We, be, A, g1, W2, b2, g2, t2, U, Un, An, mu1, var1, mu2, var2, out, am)
+        ctx.mark_non_differentiable(am)
+        ctx.set_materialize_grads(False)
+        return out, am
+
+    @staticmethod
+    def backward(ctx, dout, _dam):
+        lib = _lib()
+        h, pos, W1, We, be, A, g1, W2, b2, g2, t2, U, Un, An, mu1, var1, mu2, var2, out, am = ctx.saved_tensors
+        sc, E = ctx.scenes, ctx.E
+        eps1, eps2 = ctx.eps
+        B, bn = out.shape
+        H = h.shape[1]
+        S = sc.S
+        dev = h.device
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        wgrad = any(need[2:12])       # False: weights frozen, input gradients only
+        dpos = torch.empty(B, 2, device=dev, dtype=torch.float32) if (ctx.want_dpos and need[1]) else None
+        rows = lib.sgg_pool_norm_bwd_rows(bn)
+        nws = lib.sgg_pool_norm_bwd_ws_floats(S, B, bn)
+        if rows < 0 or nws < 0:
+            N.check(-1, "sgg_pool_norm_bwd_ws_floats")
+        ws = torch.empty(nws, device=dev, dtype=torch.float32)
+        dU = torch.empty(B, 512, device=dev, dtype=torch.float32)
+
+        def launch():
+            N.check(lib.sgg_pool_norm_bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(g1), N.ptr(W2), N.ptr(b2), N.ptr(g2),
+                                          N.ptr(t2), N.ptr(Un), N.ptr(An), N.ptr(mu1), N.ptr(var1), N.ptr(mu2),
+                                          N.ptr(var2), N.ptr(out), N.ptr(am), N.ptr(dout), N.ptr(sc.scene_off), S, B,
+                                          bn, ctx.min_n, sc.max_n, eps1, eps2, int(wgrad), N.ptr(dU), N.ptr(dpos),
+                                          N.ptr(ws), nws, N.stream_ptr()), "sgg_pool_norm_bwd")
+        launch()
+        if timer.active:
+            nb = 4.0 * (5 * B * 512 + 3 * B * bn) + 4.0 * nws
+            timer.add("sgg::pool_norm_bwd_kernel<%s> + sgg::pool_norm_finish_kernel" % ("true" if wgrad else "false"),
+                      (S, B), 3.0 * _pool_flops_bn(sc, bn), nb + _pool_wbytes(bn), launch)
+        dh = None
+        if need[0]:
+            # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
+            base = ctx.link.take() if ctx.link is not None else None
+            dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
+        if not wgrad:
+            return (dh, dpos) + (None,) * 15
+        # the two slabs' row sums, dW1h = dU^T h, the fold backward of dA; the biases in front of a BatchNorm
+        # (be, b1 through U's bias, b2) have gradient zero: exact zeros, not the rounding of a sum
+        P = bn * 512 + 2 * bn
+        slab = ws[lib.sgg_pool_norm_bwd_slab_offset(S, B):]
+        fin = slab[rows * P:]
+        FR, FC = 32, 2048            # SGG_POOL_NORM_FIN_ROWS x [dA | dgamma1 | dbeta1]
+        ws2, splits = xtw_partial(h, dU)
+        zero = torch.zeros(512, device=dev, dtype=torch.float32)
+        dW1 = torch.empty_like(W1)
+        dW2 = torch.empty(bn, 512, device=dev, dtype=torch.float32)
+        dg2 = torch.empty(bn, device=dev, dtype=torch.float32)
+        dt2 = torch.empty(bn, device=dev, dtype=torch.float32)
+        dg1 = torch.empty(512, device=dev, dtype=torch.float32)
+        dt1 = torch.empty(512, device=dev, dtype=torch.float32)
+        gf = GradFinish()
+        gf.rowsum(slab, rows, P, 0, bn * 512, dW2)
+        gf.rowsum(slab, rows, P, bn * 512, bn, dg2)
+        gf.rowsum(slab, rows, P, bn * 512 + bn, bn, dt2)
+        gf.rowsum(fin, FR, FC, 1024, 512, dg1)
+        gf.rowsum(fin, FR, FC, 1536, 512, dt1)
+        gf.xtw_sums(ws2, splits, H, 512, dW1[:, E:], trans_c=True)
+        _, dWe, _ = gf.fold(W1[:, :E], We, be, fin, FR, FC, 0, zero, 1, 512, 0, dW=dW1[:, :E])
+        gf.run()
+        return (dh, dpos, dW1, dWe, torch.zeros_like(be), torch.zeros(512, device=dev, dtype=torch.float32), dg1, dt1,
+                dW2, torch.zeros(bn, device=dev, dtype=torch.float32), dg2, dt2, None, None, None, None, None)
+
+
+class _PoolNormPos(torch.autograd.Function):
+    """_PoolNorm called once per step of the per-step rollout: one pooling net
+    at every step, so its parameter gradients are written now, not queued (see
+    _PoolPos.backward)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _PoolNorm.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, dout, _dam):
+        prev, _DEFER[0] = _DEFER[0], 0
+        try:
+            return _PoolNorm.backward(ctx, dout, _dam)
+        finally:
+            _DEFER[0] = prev
+
+
+def social_pool_norm(h, pos, pool, scenes, link=None, pos_grad=False):
+    """PoolHiddenNet core for a net built with batch_norm=1 in train()
+    (batch statistics per scene, running statistics updated): pool is the
+    module -- its Linear and BatchNorm1d layers, eps and momentum are read
+    here.  pos_grad: the positions are predictions; their gradient is
+    returned too."""
+    l1, l2 = pool_linears(pool)
+    n1, n2 = pool_norms(pool)
+    emb = pool.spatial_embedding
+    min_n = pool_norm_check(scenes, l2.weight.shape[0], (n1, n2), dropout=pool.dropout)
+    stats = tuple((float(m.eps), float(m.momentum), m.running_mean, m.running_var, m.num_batches_tracked)
+                  for m in (n1, n2))
+    op = _PoolNormPos if pos_grad else _PoolNorm
+    out, _ = op.apply(h, pos, l1.weight, emb.weight, emb.bias, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias,
+                      n2.weight, n2.bias, scenes, link, stats, min_n, bool(pos_grad))
+    return out
+
+
 def pool_linears(pool):
     """The two Linear layers of a PoolHiddenNet's mlp_pre_pool, found by type:
     built with dropout > 0 the Sequential is [Linear, ReLU, Dropout, Linear,

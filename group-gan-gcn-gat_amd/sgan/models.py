@@ -247,7 +247,12 @@ class PoolHiddenNet(nn.Module):
     nn.Dropout of mlp_pre_pool): train() runs the column-tiled family's
     dropout form with the stateless masks (K.social_pool_drop, one (seed,
     offset) of K.DROPOUT_RNG per forward), eval() the kernels of a dropout=0
-    net, bitwise."""
+    net, bitwise.  Built with batch_norm=1 (a BatchNorm1d after each Linear,
+    applied per scene to its n x n pair rows): train() runs the batch-norm
+    kernels (K.social_pool_norm: scene statistics, running statistics updated
+    in scene order, scenes of 2 .. 256 peds), eval() folds each (Linear,
+    BatchNorm1d) into one Linear (K.pool_norm_fold) and runs the kernels of a
+    batch_norm=0 net, bitwise that net's output on the folded weights."""
 
     def __init__(self, embedding_dim=64, h_dim=64, mlp_dim=1024, bottleneck_dim=1024, activation="relu",
                  batch_norm=True, dropout=0.0):
@@ -269,15 +274,29 @@ class PoolHiddenNet(nn.Module):
         """U (optional): h W1[:, E:]^T + c already computed by the encoder
         kernel's epilogue (K.pool_u_spec).  pos_grad: end_pos is a prediction
         (the per-step rollout), so the backward returns its gradient too."""
-        if self.batch_norm or self.activation != "relu":
-            raise NotImplementedError("the fused pooling kernel implements the reference configs "
-                                      "(batch_norm=0, relu)")
+        if self.activation != "relu":
+            raise NotImplementedError("the fused pooling kernel implements the reference's activation (relu)")
         if self.bottleneck_dim > K.POOL_BN_MAX:    # refused before any launch
             raise K.N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
                                 "(SGG_POOL_BN_MAX)" % (self.bottleneck_dim, K.POOL_BN_MAX))
         sc = _scenes(seq_start_end, end_pos.device, scenes)
         l1, l2 = K.pool_linears(self)
         emb = self.spatial_embedding
+        if self.batch_norm:
+            # never on U from an encoder epilogue, no dh handoff (fused_ok() is False, so no caller passes either)
+            sc.pool_plan(self.bottleneck_dim, batch_norm=True)   # a fixed-capacity batch refuses, naming batch_norm
+            hs = h_states.reshape(-1, self.h_dim)
+            if self.training:
+                # batch statistics per scene: the batch-norm kernels (sgg_pool_norm_*), at every width
+                return K.social_pool_norm(hs, end_pos, self, sc, link=link, pos_grad=pos_grad)
+            # eval(): each (Linear, BatchNorm1d) is one Linear; the kernels of a batch_norm=0 net of this width
+            n1, n2 = K.pool_norms(self)
+            K.pool_norm_modules_check((n1, n2))
+            W1, b1 = K.pool_norm_fold(l1, n1)
+            W2, b2 = K.pool_norm_fold(l2, n2)
+            if pos_grad:
+                return K.social_pool_pos(hs, end_pos, W1, emb.weight, emb.bias, b1, W2, b2, sc)
+            return K.social_pool(hs, end_pos, W1, emb.weight, emb.bias, b1, W2, b2, sc, link=link)
         if self.dropout > 0 and self.training:
             # the dropout form: never on U from an encoder epilogue, no dh handoff (fused_ok() is False, so
             # no caller passes either)

@@ -78,7 +78,8 @@ class SceneIndex:
     POOL_WIDE_TARGET_CHUNKS = int(__import__("os").environ.get("SGG_POOL_WIDE_TARGET_CHUNKS", "2048"))
     POOL_MAX_GPW = int(__import__("os").environ.get("SGG_POOL_MAX_GPW", "0"))
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False, family_bn=False, dropout=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, wide=False, family_bn=False, dropout=False,
+                  batch_norm=False):
         """Device chunk table for sgg_pool_fwd (built on the host by
         sgg_pool_plan, cached per bottleneck width); bf16: the table of
         sgg_pool_fwd_bf16 (sgg_pool_plan_bf16: big chunks, one per CU);
@@ -88,7 +89,12 @@ class SceneIndex:
         every scene size, fp32 only -- the row chunks are shared by the
         launch's column tiles, so the target is divided by their number);
         dropout: the caller's statement that the launch is the family's
-        dropout form (the same table; a fixed-capacity batch refuses it)."""
+        dropout form (the same table; a fixed-capacity batch refuses it);
+        batch_norm: the caller's statement that the pooling net was built with
+        batch_norm=1 -- its kernels (sgg_pool_norm_*) own whole scenes and take
+        no chunk table (None here); a fixed-capacity batch refuses it."""
+        if batch_norm:
+            return None
         if family_bn:
             target_chunks = target_chunks or max(8, self.POOL_WIDE_TARGET_CHUNKS // ((bn + 63) // 64))
         target_chunks = target_chunks or (self.POOL_WIDE_TARGET_CHUNKS if wide else
@@ -284,11 +290,18 @@ class PaddedScenes(SceneIndex):
         """Offset of plan k: [chunk count, 0, 0, 0 | pool_cap x (scene, i0, i1, gpw)]."""
         return self._plan_base + (4 + 4 * self.pool_cap) * k
 
-    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False, family_bn=False, dropout=False):
+    def pool_plan(self, bn, target_chunks=None, rep=1, bf16=False, family_bn=False, dropout=False,
+                  batch_norm=False):
         """(chunk table, grid basis, max rows, gpw, device chunk count): the
         table holds up to pool_cap chunks; the kernels walk the device count,
         the grid is sized by the chunk count of the batch that registered the
         plan (the capture's)."""
+        if batch_norm:
+            # BatchNorm averages over a scene's real pair rows; the padded-batch contract is pinned for the
+            # batch_norm=0 kernels only
+            raise NotImplementedError("PaddedScenes: a pooling net built with batch_norm=1 is not supported "
+                                      "(padded batches run the batch_norm=0 pooling kernels only); use SceneIndex "
+                                      "batches (scripts/train.py --batch_norm)")
         if dropout:
             # the dropout form lives in the column-tiled family, which has no fixed-capacity plan
             raise NotImplementedError("PaddedScenes: a pooling net with dropout > 0 in training is not supported "
@@ -430,9 +443,10 @@ class _PaddedRepeat(SceneIndex):
     def ped_scene_long(self):
         raise NotImplementedError("PaddedScenes.repeat: no ped-scene map")
 
-    def pool_plan(self, bn, target_chunks=None, bf16=False, family_bn=False, dropout=False):
+    def pool_plan(self, bn, target_chunks=None, bf16=False, family_bn=False, dropout=False, batch_norm=False):
         # (the fixed-capacity plan serves both precisions: the bf16 kernel takes any chunk table)
-        return self.parent.pool_plan(bn, target_chunks, rep=self.k, family_bn=family_bn, dropout=dropout)
+        return self.parent.pool_plan(bn, target_chunks, rep=self.k, family_bn=family_bn, dropout=dropout,
+                                     batch_norm=batch_norm)
 
     def groups(self, labels):
         raise NotImplementedError("PaddedScenes: the per-op group index is not captured")
@@ -443,6 +457,7 @@ SGG_POOL_WIDE_MAX_PEDS = 1024   # include/sgg.h: scene bound of the tiled (wide)
 SGG_GAT_MAX_NODES = 128         # include/sgg.h: segment bound of the LDS-resident attention kernels
 SGG_GAT_WIDE_MAX_NODES = 1024   # include/sgg.h: segment bound of the tiled (wide) attention kernels
 SGG_POOL_BN_MAX = 1024          # include/sgg.h: bottleneck bound of the column-tiled pooling kernels
+SGG_POOL_NORM_MAX_PEDS = 256     # include/sgg.h: scene bound of the batch-norm pooling kernels in train()
 POOL_BUILT_BN = (8, 16, 32, 48, 64)   # widths of the resident / wide pooling kernels (pool.hip, pool_wide.hip)
 SGG_POOL_MAX_ROWS = 64   # chunk height bound of sgg_pool_fwd (a padded plan's LDS is sized for it)
 

@@ -1460,6 +1460,61 @@ int sgg_pool_dpos_drop(const float* U, const float* pos, const float* A, const f
                        float* dpos, float p, unsigned long long seed, unsigned offset,
                        const unsigned long long* rng_dev, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Social pooling with batch norm in train(): the pooling net built with
+ * batch_norm=1 (mlp_pre_pool = Linear, BatchNorm1d, ReLU, Linear,
+ * BatchNorm1d, ReLU), both BatchNorms on ONE scene's n x n pair rows
+ * (biased statistics, self pairs included).  fp32, every bn in
+ * 1 .. SGG_POOL_BN_MAX, scenes of 2 .. SGG_POOL_NORM_MAX_PEDS peds
+ * (min_n / max_n: the batch's smallest and largest scene; a scene of one
+ * ped has one value per channel and is SGG_E_ARG).  No atomics, every sum
+ * in a fixed order.  U, pos, A, W2, b2, scene_off as sgg_pool_fwd_bn's;
+ * gamma1 / beta1 (512), gamma2 / beta2 (bn) the BatchNorm weights.
+ *
+ * sgg_pool_norm_fwd writes
+ *   mu1, var1 (S x 512)  first-layer statistics per scene, in closed form:
+ *                        mean_j U[j, k], var_j(U[j, k] + p_j . A_k) + var_i(p_i . A_k)
+ *   Un (B x 512), An (S x 512 x 2)  BatchNorm 1 folded: g (U - mu1) + beta1, g A,
+ *                        g = gamma1 / sqrt(var1 + eps1)
+ *   mu2, var2 (S x bn)   second-layer statistics (count / mean / M2 merged per pair tile)
+ *   out, argmax (B x bn) max_j relu(g2 (y2 - mu2) + beta2), the affine map before
+ *                        the max; argmax the global ped index, smallest j on ties.
+ * sgg_pool_norm_running: r <- (1 - momentum) r + momentum stat_s for s = 0 .. S-1
+ * in scene order, the variance unbiased (n^2 / (n^2 - 1)); mean / var are
+ * S x C (mu1 / var1 with C = 512, mu2 / var2 with C = bn).  momentum outside
+ * [0, 1] is SGG_E_ARG.
+ * sgg_pool_norm_bwd: dU (B x 512: the gradient of U), dpos (B x 2, or NULL)
+ * and, with wgrad != 0, the parameter-gradient slabs in ws, from float
+ * sgg_pool_norm_bwd_slab_offset(S, B) on:
+ *   rows = sgg_pool_norm_bwd_rows(bn) rows of [dW2 (bn x 512) | dgamma2 (bn) | dbeta2 (bn)],
+ *   then SGG_POOL_NORM_FIN_ROWS rows of [dA (512 x 2) | dgamma1 (512) | dbeta1 (512)];
+ * the gradients are the sums over the rows.  db2 and the gradient of U's bias
+ * are mathematically zero and not formed.  ws holds
+ * sgg_pool_norm_bwd_ws_floats(S, B, bn) floats: the two slabs (their size does
+ * not depend on the batch) and 3 B x 512 + 4 S x 512 floats of per-ped sums
+ * (two of them kept in double; ws must be 8-byte aligned).
+ * NULL operands, bn / scene sizes out of range, eps not positive and finite
+ * and a short workspace are SGG_E_ARG before any launch. */
+#define SGG_POOL_NORM_MAX_PEDS 256
+#define SGG_POOL_NORM_FIN_ROWS 32
+int sgg_pool_norm_fwd(const float* U, const float* pos, const float* A, const float* gamma1,
+                      const float* beta1, const float* W2, const float* b2, const float* gamma2,
+                      const float* beta2, const int32_t* scene_off, int S, int B, int bn, int min_n,
+                      int max_n, float eps1, float eps2, float* Un, float* An, float* mu1, float* var1,
+                      float* mu2, float* var2, float* out, int32_t* argmax, void* stream);
+int sgg_pool_norm_running(const float* mean, const float* var, const int32_t* scene_off, int S, int C,
+                          float momentum, float* running_mean, float* running_var, void* stream);
+int sgg_pool_norm_bwd_rows(int bn);
+long long sgg_pool_norm_bwd_ws_floats(int S, int B, int bn);
+long long sgg_pool_norm_bwd_slab_offset(int S, int B);
+int sgg_pool_norm_bwd(const float* U, const float* pos, const float* A, const float* gamma1,
+                      const float* W2, const float* b2, const float* gamma2, const float* beta2,
+                      const float* Un, const float* An, const float* mu1, const float* var1,
+                      const float* mu2, const float* var2, const float* out, const int32_t* argmax,
+                      const float* dout, const int32_t* scene_off, int S, int B, int bn, int min_n,
+                      int max_n, float eps1, float eps2, int wgrad, float* dU, float* dpos, float* ws,
+                      size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

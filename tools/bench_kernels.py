@@ -1,5 +1,5 @@
 """Micro-benchmarks of single kernels on the training shapes (HIP events on
-the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|poolbn|pooldrop|gatwide|gatdrop|...]
+the launch stream).  Usage: python tools/bench_kernels.py [pool|big|lstm|poolwide|poolbn|pooldrop|poolnorm|gatwide|gatdrop|...]
 validate [a|b]: wall time of one check_accuracy pass, three routes; valkernel: sgg_val_metrics alone."""
 import os
 import sys
@@ -194,6 +194,59 @@ def pooldrop(S, n, bn, p=0.5, reps=20):
             name, S, n, bn, p if name == "drop" else 0.0, uf, ub0, ub), flush=True)
     print("pool ratio S=%3d n=%4d bn=%4d        fwd %8.2f x   bwd(dU only) %8.2f x   bwd %8.2f x" % (
         (S, n, bn) + tuple(d / q for d, q in zip(res["drop"], res["plain"]))), flush=True)
+
+
+def poolnorm(S, n, bn, reps=10):
+    """The batch-norm pooling kernels in train() (sgg_pool_norm_fwd: first-layer
+    statistics, second-layer statistics, apply; sgg_pool_norm_bwd: the dense
+    pass and the finish, with and without weight gradients) beside the plain
+    column-tiled launches (sgg_pool_fwd_bn / sgg_pool_bwd_bn) on the same
+    operands.  Device events around reps launches after 3 warm-ups (timeit)."""
+    torch.manual_seed(0)
+    dev = "cuda"
+    B = S * n
+    sc = SceneIndex(np.arange(0, B + 1, n), dev)
+    U = torch.randn(B, 512, device=dev) * 0.3
+    pos = torch.rand(B, 2, device=dev) * 15
+    A = torch.randn(512, 2, device=dev) * 0.3
+    W2 = torch.randn(bn, 512, device=dev) * 0.05
+    b2 = torch.randn(bn, device=dev) * 0.1
+    g1, t1 = 1 + 0.3 * torch.randn(512, device=dev), 0.3 * torch.randn(512, device=dev)
+    g2, t2 = 1 + 0.3 * torch.randn(bn, device=dev), 0.3 * torch.randn(bn, device=dev)
+    dout = torch.randn(B, bn, device=dev)
+    lib = N.load()
+    out = torch.empty(B, bn, device=dev)
+    am = torch.empty(B, bn, device=dev, dtype=torch.int32)
+    dU = torch.empty(B, 512, device=dev)
+    chunks, nchunks, max_rows, g = sc.pool_plan(bn, family_bn=True)
+    part = torch.empty(lib.sgg_pool_bwd_bn_ws_floats(S, B, bn, n), device=dev)
+    fwd = lambda: N.check(lib.sgg_pool_fwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(sc.scene_off),
+                                              N.ptr(chunks), nchunks, max_rows, g, B, bn, sc.max_n, N.ptr(out),
+                                              N.ptr(am), N.stream_ptr()), "fwd")
+    bwd_p = lambda p, nf: N.check(lib.sgg_pool_bwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                                      N.ptr(dout), N.ptr(sc.scene_off), S, B, bn, sc.max_n, N.ptr(dU),
+                                                      N.ptr(p), nf, N.stream_ptr()), "bwd")
+    plain = (timeit(fwd, reps), timeit(lambda: bwd_p(None, 0), reps), timeit(lambda: bwd_p(part, part.numel()), reps))
+    Un, An = torch.empty(B, 512, device=dev), torch.empty(S, 1024, device=dev)
+    mu1, var1 = torch.empty(S, 512, device=dev), torch.empty(S, 512, device=dev)
+    mu2, var2 = torch.empty(S, bn, device=dev), torch.empty(S, bn, device=dev)
+    dpos = torch.empty(B, 2, device=dev)
+    ws = torch.empty(lib.sgg_pool_norm_bwd_ws_floats(S, B, bn), device=dev)
+    nfwd = lambda: N.check(lib.sgg_pool_norm_fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(g1), N.ptr(t1), N.ptr(W2),
+                                                 N.ptr(b2), N.ptr(g2), N.ptr(t2), N.ptr(sc.scene_off), S, B, bn, n, n,
+                                                 1e-5, 1e-5, N.ptr(Un), N.ptr(An), N.ptr(mu1), N.ptr(var1), N.ptr(mu2),
+                                                 N.ptr(var2), N.ptr(out), N.ptr(am), N.stream_ptr()), "norm fwd")
+    nbwd = lambda w: N.check(lib.sgg_pool_norm_bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(g1), N.ptr(W2), N.ptr(b2),
+                                                   N.ptr(g2), N.ptr(t2), N.ptr(Un), N.ptr(An), N.ptr(mu1), N.ptr(var1),
+                                                   N.ptr(mu2), N.ptr(var2), N.ptr(out), N.ptr(am), N.ptr(dout),
+                                                   N.ptr(sc.scene_off), S, B, bn, n, n, 1e-5, 1e-5, w, N.ptr(dU),
+                                                   N.ptr(dpos), N.ptr(ws), ws.numel(), N.stream_ptr()), "norm bwd")
+    norm = (timeit(nfwd, reps), timeit(lambda: nbwd(0), reps), timeit(lambda: nbwd(1), reps))
+    for name, (uf, ub0, ub) in (("plain", plain), ("norm", norm)):
+        print("pool %-5s S=%3d n=%4d bn=%4d  fwd %10.1f us  bwd(dU only) %10.1f us  bwd %10.1f us" % (
+            name, S, n, bn, uf, ub0, ub), flush=True)
+    print("pool ratio S=%3d n=%4d bn=%4d  fwd %10.2f x   bwd(dU only) %10.2f x   bwd %10.2f x  ws %.1f MB" % (
+        (S, n, bn) + tuple(d / q for d, q in zip(norm, plain)) + (ws.numel() * 4 / 1e6,)), flush=True)
 
 
 def gatwide(S, n, heads, F, reps=20):
@@ -521,6 +574,11 @@ if __name__ == "__main__":
     if what == "pooldrop":   # what the two dropout masks cost inside the column-tiled pooling kernels
         for bn in (8, 64, 1024):
             pooldrop(64, 20, bn)
+        sys.exit(0)
+    if what == "poolnorm":   # the batch-norm pooling kernels in train() beside the plain column-tiled launches
+        for S in (64, 512):
+            for bn in (8, 64, 1024):
+                poolnorm(S, 20, bn)
         sys.exit(0)
     if what == "gatwide":   # the tiled attention kernels above 128 nodes, next to the resident ones at 128
         for (S, n) in ((32, 128), (8, 256), (1, 1024)):
