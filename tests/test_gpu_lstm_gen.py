@@ -42,82 +42,7 @@ def close(a, b, rtol=1e-4, floor=1e-6, what=""):
 # ---------------------------------------------------------------------------
 # 1. kernels against the oracle's modules, float64 yardstick
 # ---------------------------------------------------------------------------
-def _build(H, Tn, decoder, seed):
-    from oracle import sgan_oracle as O
-    torch.manual_seed(seed)
-    return O.Decoder(Tn, 16, H, 64, 1, False) if decoder else O.Encoder(16, H)
-
-
-def _inputs(H, Tn, decoder, B, seed):
-    gen = torch.Generator().manual_seed(seed + 1)
-    if decoder:
-        return dict(last_pos=torch.randn(B, 2, generator=gen), last_rel=torch.randn(B, 2, generator=gen) * 0.3,
-                    h0=torch.randn(1, B, H, generator=gen) * 0.5, dy=torch.randn(Tn, B, 2, generator=gen))
-    return dict(rel=torch.randn(Tn, B, 2, generator=gen) * 0.3, dy=torch.randn(1, B, H, generator=gen))
-
-
-def _run(mod, inp, decoder, dev, dtype):
-    """Outputs, input gradients and parameter gradients of one module run."""
-    c = lambda t: t.detach().to(device=dev, dtype=dtype)
-    mod.zero_grad()
-    if decoder:
-        h0 = c(inp["h0"]).requires_grad_(True)
-        lr = c(inp["last_rel"]).requires_grad_(True)
-        y, _ = mod(c(inp["last_pos"]), lr, (h0, torch.zeros_like(h0)), None)
-        (y * c(inp["dy"])).sum().backward()
-        res = {"out": y, "dh0": h0.grad, "drel": lr.grad}
-    else:
-        rel = c(inp["rel"]).requires_grad_(True)
-        y = mod(rel)
-        (y.reshape(inp["dy"].shape) * c(inp["dy"])).sum().backward()
-        res = {"out": y.reshape(inp["dy"].shape), "drel": rel.grad}
-    for k, p in mod.named_parameters():
-        res["d" + k] = p.grad
-    return {k: v.detach().cpu().double().numpy() for k, v in res.items()}
-
-
-_REF = {}
-
-
-def reference(H, Tn, decoder, B):
-    """(module, inputs, float64 results, fp32 CPU results) of a case, computed
-    once and shared."""
-    key = (H, Tn, decoder, B)
-    if key not in _REF:
-        seed = 1000 * H + 10 * Tn + B
-        ref = _build(H, Tn, decoder, seed)
-        inp = _inputs(H, Tn, decoder, B, seed)
-        r32 = _run(ref, inp, decoder, "cpu", torch.float32)
-        torch.set_default_dtype(torch.float64)
-        try:
-            r64 = _run(copy.deepcopy(ref).double(), inp, decoder, "cpu", torch.float64)
-        finally:
-            torch.set_default_dtype(torch.float32)
-        _REF[key] = (ref, inp, r64, r32)
-    return _REF[key]
-
-
-def gate(tag, got, r64, r32, sel=lambda k, a: a):
-    """Every quantity within 4x the fp32 CPU error + 1e-6 of the scale; prints
-    each figure, then asserts."""
-    bad = []
-    for k in r64:
-        ref = sel(k, r64[k])
-        e = float(np.abs(sel(k, got[k]) - ref).max())
-        e32 = float(np.abs(sel(k, r32[k]) - ref).max())
-        scale = float(np.abs(ref).max())
-        bound = 4 * e32 + 1e-6 * scale
-        print("%s %-28s err %.3e  cpu32 %.3e  ratio %6.2f  scale %.3e" % (tag, k, e, e32, e / max(e32, 1e-300), scale))
-        if not e <= bound:
-            bad.append((k, e, e32, scale))
-    assert not bad, (tag, bad)
-
-
-def hip_module(ref, H, Tn, decoder):
-    from sgan import models as M
-    mod = M.Decoder(Tn, 16, H, 64, 1, False) if decoder else M.Encoder(16, H)
-    mod.load_state_dict(ref.state_dict())
-    return mod.to(DEV)
+from _lstm_ref import _build, _inputs, _run, reference, gate, hip_module  # noqa: E402,F401  (tests/_lstm_ref.py)
 
 
 CASES = [(8, 8, False, 17), (8, 3, True, 1), (40, 1, False, 33), (40, 12, True, 16), (40, 8, False, 16),
