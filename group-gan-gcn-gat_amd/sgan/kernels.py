@@ -5,6 +5,7 @@ backward are hand-written HIP kernels, the parameter-gradient reductions over
 all nodes (X^T dY, column sums) included (sgg_xtw, xtw.hip).  No op has a CPU
 path.
 """
+import collections
 import contextlib
 import ctypes
 import functools
@@ -1238,220 +1239,333 @@ def pool_is_wide(scenes):
     return scenes.max_n > SGG_POOL_MAX_PEDS
 
 
+def _pool_bn_bound(bn):
+    if bn > POOL_BN_MAX:
+        raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
+                            "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
+
+
+def _pool_operands(h, pos, W1, We, be, b1, W2, b2, scenes, U=None, plan=None, prec=None):
+    """The pooling ops' forward prologue -> (h, pos, W1, W2, b2, A, U, out,
+    argmax, plan): the operands checked and contiguous, one fold launch
+    (A = W1e We, c = W1e be + b1), U = h W1h^T + c (sgg_xw on the W1h block
+    in place) unless the encoder kernel's epilogue already produced it, the
+    two outputs.  The width's bound and plan(scenes, bn, False) -- a family's
+    whose lookup may refuse -- come before the first launch."""
+    h = _rows(h, "h")
+    pos = _req(pos, "pos").contiguous()
+    B, Hd = h.shape
+    E = We.shape[0]
+    bn = W2.shape[0]
+    assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
+    assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
+    _pool_bn_bound(bn)
+    if plan is not None:
+        plan = plan(scenes, bn, False)
+    W1, W2, b2 = W1.contiguous(), W2.contiguous(), b2.contiguous()
+    A, c = fold_fwd(W1[:, :E], We, be, b1)
+    if U is None:
+        U = xw_raw(h, W1[:, E:], c, trans_w=True, prec=prec)             # B x 512
+    else:                                                     # from the encoder kernel's epilogue
+        assert U.shape == (B, 512) and U.is_contiguous()
+    out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
+    am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
+    return h, pos, W1, W2, b2, A, U, out, am, plan
+
+
+def _pool_save(ctx, scenes, E, link, am, *saved):
+    """The pooling ops' forward epilogue."""
+    ctx.scenes, ctx.E, ctx.link = scenes, E, link
+    ctx.save_for_backward(*saved)
+    ctx.mark_non_differentiable(am)
+    ctx.set_materialize_grads(False)   # no zero-filled gradient for the argmax output
+
+
+def _pool_alone(launch, scenes, bn, fscale, flops, nbytes, name, *name_args):
+    """Issue a pooling forward that is neither held nor carried by the paired
+    launch.  The flop model and the name (a string, or a function of
+    name_args) are evaluated only for a timer record."""
+    rider = _PRIDER[0]
+    if rider is not None:
+        rider.flush()    # a held forward goes out first, on its own
+    launch()
+    if timer.active:
+        timer.add(name if isinstance(name, str) else name(*name_args), (scenes.S, scenes.B), fscale * flops(scenes, bn),
+                  nbytes + _pool_wbytes(bn), launch)
+
+
+def _pool_batch(U, pos, scenes, chunks, nchunks, max_rows, gpw, out, am, ncd):
+    """-> (one batch of the paired launch (SggPoolBatch), the tensors its pointers name)."""
+    return (N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw,
+                        scenes.B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd)),
+            (U, pos, scenes.scene_off, chunks, out, am, ncd))
+
+
+def _pool_dh(dU, W1h, out, acc):
+    """dh = dU W1h into out (None: a new buffer); acc: added to what out holds
+    (the other consumer's gradient of h) in the same launch."""
+    return xw_raw(dU, W1h, None, trans_w=False, prec="fp32", out=out, act=2 if acc else 0)
+
+
+def _pool_dh_dw(dU, W1h, dh, acc, h, ws):
+    """dh = dU W1h (+ dh) and the h^T dU partials (+ column sums) into ws in
+    ONE launch; issues it and returns it."""
+    lib = _lib()
+    B, H = dh.shape
+
+    def launch():
+        N.check(lib.sgg_pool_dh_dw(N.ptr(dU), 512, N.ptr(W1h), W1h.stride(0), N.ptr(dh), dh.stride(0), int(acc),
+                                   N.ptr(h), h.stride(0), B, H, N.ptr(ws), ws.numel() * 4, N.stream_ptr()),
+                "sgg_pool_dh_dw")
+    launch()
+    return launch
+
+
+def _pool_slab(rows, bn):
+    """-> (rows, floats) of a slab of `rows` rows [dW2 | dA | db2]."""
+    return rows, rows * (bn * 512 + 1024 + bn)
+
+
+def _pool_bn_slab(lib, sc, B, bn):
+    """The column-tiled backward's workspace -> (the slab's rows, floats: the
+    slab, then the first launch's dA partials), as the library reports them."""
+    rows = lib.sgg_pool_bwd_bn_grid(sc.S, bn, sc.max_n)
+    nws = lib.sgg_pool_bwd_bn_ws_floats(sc.S, B, bn, sc.max_n)
+    if rows < 0 or nws < 0:
+        N.check(-1, "sgg_pool_bwd_bn_ws_floats")
+    return rows, nws
+
+
+def _pool_param_grads(h, W1, We, be, E, bn, dU, part, rows, ws, splits):
+    """-> (dW1, dWe, dbe, dc, dW2, db2) in one launch after the dW1h partials
+    (ws None: formed here): dW2, db2 (slab [dW2 | dA | db2] row sums),
+    dW1h = dU^T h, dc = sum_j dU_j, and the fold backward of (dA, dc) -> dW1e,
+    dWe, dbe; dW1 assembled in place (left block, transposed right block)."""
+    if ws is None:
+        ws, splits = xtw_partial(h, dU, colsum=True)
+    H = h.shape[1]
+    P = bn * 512 + 1024 + bn
+    dW1 = torch.empty_like(W1)
+    dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
+    db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
+    dc = torch.empty(512, device=h.device, dtype=torch.float32)
+    gf = GradFinish()
+    gf.rowsum(part, rows, P, 0, bn * 512, dW2)
+    gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
+    gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
+    _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
+                          dW=dW1[:, :E])
+    gf.run()   # (with riding partials: queued, issued after the encoder's backward has written them)
+    return dW1, dWe, dbe, dc, dW2, db2
+
+
+@contextlib.contextmanager
+def _grads_written_now():
+    """Around the backward of a pooling op of the per-step rollout: the loop
+    calls one pooling net at every step, so autograd SUMS this op's parameter
+    gradients with the other steps': they must be written now, not at the
+    trainer's grad_flush (defer_grad_finish's invariant -- no parameter feeds
+    two ops -- does not hold here)."""
+    prev, _DEFER[0] = _DEFER[0], 0
+    try:
+        yield
+    finally:
+        _DEFER[0] = prev
+
+
+def _pool_bwd_name(bn, wg, sc):
+    jq = max(1, min(8, 256 // sc.S)) if sc.S >= 1 else 1   # pool.hip pool_bwd_jq / launch_bwd
+    stage = (sc.max_n + jq - 1) // jq + 1 <= 16
+    return "sgg::pool_bwd_kernel<%d, %s, %s>" % (bn, wg, "true" if stage else "false")
+
+
+def _pool_bn_bwd_name(tag):
+    # (the column-tiled family: its dU launch and, with weight gradients, its dW2 launch, timed together)
+    both = "sgg::pool_bwd_bn_du%s_kernel<true> + sgg::pool_bwd_bn_dw%s_kernel" % (tag, tag)
+    return lambda bn, wg, sc: both if wg == "true" else "sgg::pool_bwd_bn_du%s_kernel<false>" % tag
+
+
+# What one family of pooling kernels needs beyond _Pool's shared text:
+#   fwd, bwd, dpos  the library's entry points (resident in the bf16 precision: sgg_pool_fwd_bf16)
+#   ncd             the forward's last argument is a fixed-capacity plan's device chunk count
+#   coltiled        column-tiled: the backward also takes its workspace's size, and -- the dropout form -- both
+#                   directions and dpos take (p, seed, offset, no mask dump) last
+#   dual            the backward may form dh and the h^T dU partials in ONE launch (DUAL_POOL_BWD); the dropout
+#                   form keeps the two launches it was measured with
+#   plan            (scenes, bn, bf16) -> the chunk plan; early: looked up ahead of the fold and the U product,
+#                   where a fixed-capacity batch (PaddedScenes) refuses the family by name
+#   slab            (lib, scenes, B, bn) -> (rows, floats) of the backward's [dW2 | dA | db2] slab
+#   flops           the forward's flop model (the column-tiled forward forms the hidden units once per tile of 64
+#                   columns); fwd_name: the forward kernel, a string or a function of (bn, gpw, chunks, bf16,
+#                   device, max_n, max_rows); bwd_name: (bn, "true" / "false" for weight gradients, scenes)
+_PoolFamily = collections.namedtuple(
+    "_PoolFamily", "fwd bwd dpos ncd coltiled dual plan early slab flops fwd_name bwd_name")
+# scenes of up to SGG_POOL_MAX_PEDS at a built width: fp32 / bf16, the only family that joins the paired launch
+# (pool_pair) and hands dh to the encoder's backward (PoolDhSlot)
+_POOL_RESIDENT = _PoolFamily(
+    "sgg_pool_fwd", "sgg_pool_bwd", "sgg_pool_dpos", True, False, True,
+    lambda sc, bn, bf16: sc.pool_plan(bn, bf16=bf16), False,
+    lambda lib, sc, B, bn: _pool_slab(lib.sgg_pool_bwd_grid(sc.S), bn),
+    _pool_flops, _pool_kname, _pool_bwd_name)
+# a batch with a scene above that bound: every scene of it through the tiled (wide) kernels, fp32 in either precision
+_POOL_WIDE = _PoolFamily(
+    "sgg_pool_fwd_wide", "sgg_pool_bwd_wide", "sgg_pool_dpos", False, False, True,
+    lambda sc, bn, bf16: sc.pool_plan(bn, wide=True), False,
+    lambda lib, sc, B, bn: _pool_slab(lib.sgg_pool_bwd_wide_grid(sc.S, sc.max_n), bn),
+    _pool_flops, lambda bn, gpw, *_: "sgg::pool_fwd_wide_kernel<%d, %d>" % (bn, gpw),
+    lambda bn, wg, sc: "sgg::pool_bwd_wide_kernel<%d, %s>" % (bn, wg))
+# a width pool.hip / pool_wide.hip are not built for: the column-tiled family at every scene size, fp32 too
+_POOL_BN = _PoolFamily(
+    "sgg_pool_fwd_bn", "sgg_pool_bwd_bn", "sgg_pool_dpos", False, True, True,
+    lambda sc, bn, bf16: sc.pool_plan(bn, family_bn=True), True, _pool_bn_slab,
+    _pool_flops_bn, "sgg::pool_fwd_bn_kernel", _pool_bn_bwd_name(""))
+# a pooling net built with dropout > 0, in training: the two nn.Dropout of mlp_pre_pool as the stateless masks of
+# include/sgg.h "Pooling dropout masks", on the column-tiled family's dropout form at EVERY width
+_POOL_DROP = _PoolFamily(
+    "sgg_pool_fwd_bn_drop", "sgg_pool_bwd_bn_drop", "sgg_pool_dpos_drop", False, True, False,
+    lambda sc, bn, bf16: sc.pool_plan(bn, family_bn=True, dropout=True), True, _pool_bn_slab,
+    _pool_flops_bn, "sgg::pool_fwd_bn_drop_kernel", _pool_bn_bwd_name("_drop"))
+
+
 class _Pool(torch.autograd.Function):
     """PoolHiddenNet on raw parameters: W1 (512 x (E + Hd)) = [W1e | W1h], the
-    spatial embedding (We, be), b1, W2 (bn x 512), b2.  Forward: one fold
-    launch (A = W1e We, c = W1e be + b1), U = h W1h^T + c (sgg_xw on the W1h
-    block in place), the fused pooling kernel.  Backward: the pooling
-    backward, dW1 assembled in place (fold backward -> left block, X^T dU
-    transposed -> right block)."""
+    spatial embedding (We, be), b1, W2 (bn x 512), b2.  Forward: the prologue
+    of _pool_operands, the family's fused pooling kernel.  Backward: the
+    family's pooling backward, dh = dU W1h, the parameter gradients
+    (_pool_param_grads).  drop = (p, seed, offset), one (seed, offset) per
+    forward: the dropout family.  pos_grad: the positions are predictions
+    (the per-step rollout, models.py:160, :164); the backward also returns
+    their gradient (sgg_pool_dpos) and writes the parameter gradients at
+    once."""
 
     @staticmethod
-    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, pdh=None):
+    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, pdh=None, drop=None, pos_grad=False):
         lib = _lib()
-        ctx.link = link
-        ctx.pdh = pdh    # a PoolDhSlot: the backward hands dU to the encoder's backward (social_pool)
-        # a batch with a scene above the resident kernels' bound: every scene
-        # of it through the tiled (wide) kernels, fp32 in either precision
-        wide = pool_is_wide(scenes)
-        h = _rows(h, "h")
-        pos = _req(pos, "pos").contiguous()
-        B, Hd = h.shape
-        E = We.shape[0]
-        bn = W2.shape[0]
-        assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
-        assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
-        W1 = W1.contiguous()
-        W2 = W2.contiguous()
-        b2 = b2.contiguous()
-        # a width pool.hip / pool_wide.hip are not built for: the column-tiled family at every scene
-        # size; like a wide launch fp32 in either precision, never paired, no dh handoff.  Its bound
-        # and its plan come before the first launch: a fixed-capacity batch (PaddedScenes) refuses
-        # such a width there, by name
-        fam = not pool_bn_built(bn)
-        if fam and bn > POOL_BN_MAX:
-            raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
-                                "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
-        fam_plan = scenes.pool_plan(bn, family_bn=True) if fam else None
-        tiled = wide or fam    # a tiled launch: neither held nor carried by the paired launch
-        A, c = fold_fwd(W1[:, :E], We, be, b1)
-        if U is None:
-            U = xw_raw(h, W1[:, E:], c, trans_w=True)             # B x 512
-        else:                                                     # from the encoder kernel's epilogue
-            assert U.shape == (B, 512) and U.is_contiguous()
-        out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
-        am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
+        tail = ()
+        if drop is not None:
+            p = float(drop[0])
+            if not 0.0 <= p < 1.0:
+                raise ValueError("pooling dropout p=%r outside [0, 1)" % p)
+            tail = (p, int(drop[1]) & 0xFFFFFFFFFFFFFFFF, int(drop[2]) & 0xFFFFFFFF, None)
+        wide = pool_is_wide(scenes)    # a scene above the tiled kernels' bound: ValueError before any launch
+        fam = _POOL_DROP if drop is not None else _POOL_BN if not pool_bn_built(W2.shape[0]) else \
+            _POOL_WIDE if wide else _POOL_RESIDENT
+        resident = fam is _POOL_RESIDENT
+        h, pos, W1, W2, b2, A, U, out, am, plan = _pool_operands(h, pos, W1, We, be, b1, W2, b2, scenes, U,
+                                                                 fam.plan if fam.early else None)
+        B, bn = out.shape
         # the opt-in bf16 precision: the 512 -> bn contraction on bf16 MFMA (its own chunk plan)
-        bf16 = _PRECISION == "bf16" and not tiled
-        plan = fam_plan if fam else scenes.pool_plan(bn, wide=True) if wide else scenes.pool_plan(bn, bf16=bf16)
+        bf16 = _PRECISION == "bf16" and resident
+        if not fam.early:
+            plan = fam.plan(scenes, bn, bf16)
         chunks, nchunks, max_rows, gpw = plan[:4]
         ncd = plan[4] if len(plan) > 4 else None    # a fixed-capacity plan's device chunk count
         if bf16 and ncd is not None:
             gpw = 4   # (a fixed-capacity fp32 plan: its chunks run in passes of up to 512 pairs)
+        fwd = lib.sgg_pool_fwd_bf16 if bf16 else getattr(lib, fam.fwd)
 
-        if fam:
-            def launch():
-                N.check(lib.sgg_pool_fwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
-                                            N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
-                                            scenes.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()),
-                        "sgg_pool_fwd_bn")
-            kname = lambda nch: "sgg::pool_fwd_bn_kernel"
-        elif wide:
-            def launch():
-                N.check(lib.sgg_pool_fwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
-                                              N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
-                                              scenes.max_n, N.ptr(out), N.ptr(am), N.stream_ptr()),
-                        "sgg_pool_fwd_wide")
-            kname = lambda nch: "sgg::pool_fwd_wide_kernel<%d, %d>" % (bn, gpw)
+        def launch():
+            N.check(fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(scenes.scene_off), N.ptr(chunks),
+                        nchunks, max_rows, gpw, B, bn, scenes.max_n, N.ptr(out), N.ptr(am),
+                        *((N.ptr(ncd),) if fam.ncd else tail), N.stream_ptr()), fam.fwd)
+        nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn     # + the weights, once per launch (_pool_wbytes)
+        rider = _PRIDER[0] if resident else None    # (only a resident forward is held or carried)
+        hold = rider is not None and not rider.done and rider.held is None
+        if hold or (rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw)):
+            work = (scenes.S, B, _pool_flops(scenes, bn), nb)
+            batch, keep = _pool_batch(U, pos, scenes, chunks, nchunks, max_rows, gpw, out, am, ncd)
+            if hold:
+                # the block's first pooling forward: held until the next one carries it
+                rider.hold(batch, keep, (A, W2, b2), bn, bf16, gpw, nchunks, work, launch)
+            else:
+                pl, (name, S2, B2, fl2, nb2, nch2) = rider.carry(batch, keep, nchunks, work)
+                pl()
+                if timer.active:
+                    timer.add(_pool_kname(bn, gpw, nch2, bf16, h.device, scenes.max_n, max_rows), (S2, B2, "pair"),
+                              fl2, nb2 + _pool_wbytes(bn), pl)
         else:
-            fwd = lib.sgg_pool_fwd_bf16 if bf16 else lib.sgg_pool_fwd
-
-            def launch():
-                N.check(fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2), N.ptr(scenes.scene_off),
-                            N.ptr(chunks), nchunks, max_rows, gpw, B, bn, scenes.max_n, N.ptr(out),
-                            N.ptr(am), N.ptr(ncd), N.stream_ptr()), "sgg_pool_fwd")
-            kname = lambda nch: _pool_kname(bn, gpw, nch, bf16, h.device, scenes.max_n, max_rows)
-        nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn     # + the weights, once per launch (_pool_timing)
-        # (the column-tiled forward forms the hidden units once per tile of 64 columns)
-        work = (scenes.S, B, _pool_flops_bn(scenes, bn) if fam else _pool_flops(scenes, bn), nb)
-        rider = _PRIDER[0]
-        # (a wide or column-tiled forward is neither held nor carried: it never joins the paired launch)
-        if rider is not None and not tiled and not rider.done and rider.held is None:
-            # the block's first pooling forward: held until the next one carries it
-            batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
-                                gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
-            rider.hold(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd), (A, W2, b2), bn, bf16, gpw,
-                       nchunks, work, launch)
-        elif rider is not None and rider.fits((A, W2, b2), bn, bf16, gpw, wide=tiled):
-            batch = N.PoolBatch(N.ptr(U), N.ptr(pos), N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows,
-                                gpw, B, scenes.max_n, N.ptr(out), N.ptr(am), N.ptr(ncd))
-            pl, (name, S2, B2, fl2, nb2, nch2) = rider.carry(batch, (U, pos, scenes.scene_off, chunks, out, am, ncd),
-                                                             nchunks, work)
-            pl()
-            if timer.active:
-                timer.add(kname(nch2), (S2, B2, "pair"), fl2, nb2 + _pool_wbytes(bn), pl)
-        else:
-            if rider is not None:
-                rider.flush()    # a held forward goes out first, on its own
-            launch()
-            if timer.active:
-                timer.add(kname(nchunks), (scenes.S, B), work[2], nb + _pool_wbytes(bn), launch)
-        ctx.scenes = scenes
-        ctx.E = E
-        ctx.save_for_backward(h, pos, W1, We, be, A, W2, U, out, am)
-        ctx.mark_non_differentiable(am)
-        ctx.set_materialize_grads(False)   # no zero-filled gradient for the argmax output
+            _pool_alone(launch, scenes, bn, 1.0, fam.flops, nb, fam.fwd_name, bn, gpw, nchunks, bf16, h.device,
+                        scenes.max_n, max_rows)
+        ctx.fam, ctx.tail, ctx.pos_grad = fam, tail, pos_grad
+        ctx.pdh = pdh if resident else None    # a PoolDhSlot: the backward hands dU to the encoder's backward
+        _pool_save(ctx, scenes, We.shape[0], link, am, h, pos, W1, We, be, A, W2, U, out, am)
         return out, am
 
     @staticmethod
     def backward(ctx, dout, _dam):
+        dout = dout.contiguous()
+        if not ctx.pos_grad:
+            return _Pool._grads(ctx, dout)
+        with _grads_written_now():
+            grads = _Pool._grads(ctx, dout)
+        if not ctx.needs_input_grad[1]:
+            return grads
+        _h, pos, _W1, _We, _be, A, W2, U, out, am = ctx.saved_tensors
+        sc = ctx.scenes
+        B, bn = out.shape
+        dpos = torch.empty(B, 2, device=pos.device, dtype=torch.float32)
+        N.check(getattr(_lib(), ctx.fam.dpos)(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
+                                              N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, N.ptr(dpos), *ctx.tail,
+                                              N.stream_ptr()), ctx.fam.dpos)
+        return grads[:1] + (dpos,) + grads[2:]
+
+    @staticmethod
+    def _grads(ctx, dout):
         lib = _lib()
         h, pos, W1, We, be, A, W2, U, out, am = ctx.saved_tensors
-        sc, E = ctx.scenes, ctx.E
+        sc, E, fam, tail = ctx.scenes, ctx.E, ctx.fam, ctx.tail
         B, bn = out.shape
-        dout = dout.contiguous()
         need = ctx.needs_input_grad
         wgrad = any(need[2:8])       # False: weights frozen (the G-step's discriminator), input gradient only
-        P = bn * 512 + 1024 + bn
         dU = torch.empty(B, 512, device=h.device, dtype=torch.float32)
-        wide = pool_is_wide(sc)
-        fam = not pool_bn_built(bn)
-        if fam:
-            # the slab's rows, then the first launch's dA partials: the size the library reports
-            rows = lib.sgg_pool_bwd_bn_grid(sc.S, bn, sc.max_n)
-            nws = lib.sgg_pool_bwd_bn_ws_floats(sc.S, B, bn, sc.max_n)
-            if rows < 0 or nws < 0:
-                N.check(-1, "sgg_pool_bwd_bn_ws_floats")
-            part = torch.empty(nws, device=h.device, dtype=torch.float32) if wgrad else None
-        else:
-            rows = lib.sgg_pool_bwd_wide_grid(sc.S, sc.max_n) if wide else lib.sgg_pool_bwd_grid(sc.S)
-            part = torch.empty(rows, P, device=h.device, dtype=torch.float32) if wgrad else None
+        rows, nws = fam.slab(lib, sc, B, bn)
+        part = torch.empty(nws, device=h.device, dtype=torch.float32) if wgrad else None
+        bwd = getattr(lib, fam.bwd)
+
         def launch():
-            if fam:
-                N.check(lib.sgg_pool_bwd_bn(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
-                                            N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
-                                            N.ptr(part), part.numel() if wgrad else 0, N.stream_ptr()),
-                        "sgg_pool_bwd_bn")
-                return
-            if wide:
-                N.check(lib.sgg_pool_bwd_wide(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
-                                              N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
-                                              N.ptr(part), N.stream_ptr()), "sgg_pool_bwd_wide")
-                return
-            N.check(lib.sgg_pool_bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout),
-                                     N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU), N.ptr(part),
-                                     N.stream_ptr()), "sgg_pool_bwd")
+            N.check(bwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout),
+                        N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU), N.ptr(part),
+                        *((nws if wgrad else 0,) + tail if fam.coltiled else ()), N.stream_ptr()), fam.bwd)
         launch()
         if timer.active:
-            nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * part.numel() if wgrad else 0.0)
-            jq = max(1, min(8, 256 // sc.S)) if sc.S >= 1 else 1   # pool.hip pool_bwd_jq / launch_bwd
-            stage = (sc.max_n + jq - 1) // jq + 1 <= 16
-            # (the column-tiled family: its dU launch and, with weight gradients, its dW2 launch, timed together)
-            name = "sgg::pool_bwd_bn_du_kernel<%s>%s" % (("true", " + sgg::pool_bwd_bn_dw_kernel") if wgrad
-                                                        else ("false", "")) if fam else \
-                "sgg::pool_bwd_wide_kernel<%d, %s>" % (bn, "true" if wgrad else "false") if wide else \
-                "sgg::pool_bwd_kernel<%d, %s, %s>" % (bn, "true" if wgrad else "false", "true" if stage else "false")
-            timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
-        dh = None
+            nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * nws if wgrad else 0.0)
+            timer.add(fam.bwd_name(bn, "true" if wgrad else "false", sc), (sc.S, B), 8.0 * B * bn * 512, nb, launch)
+        dh = ws = None
+        splits = 0
         H = h.shape[1]
-        dual = need[0] and wgrad and DUAL_POOL_BWD and H <= 64
-        # armed (social_pool): neither product is launched here -- the encoder's backward forms dh in its
-        # prologue and carries the h^T dU partials (sgg_lstm_bwd_pooldh); what is returned as the gradient of
-        # h is only the buffer by which that backward recognises its source
-        hand = ctx.pdh is not None and need[0] and not wide and not fam and (dual or not wgrad)
         if need[0]:
+            W1h = W1[:, E:]
             base = ctx.link.take() if ctx.link is not None else None
-            if hand:
+            dual = wgrad and DUAL_POOL_BWD and fam.dual and H <= 64
+            if ctx.pdh is not None and (dual or not wgrad):
+                # armed (social_pool): neither product is launched here -- the encoder's backward forms dh in
+                # its prologue and carries the h^T dU partials (sgg_lstm_bwd_pooldh); what is returned as the
+                # gradient of h is only the buffer by which that backward recognises its source
                 dh = base if base is not None else torch.empty(B, H, device=h.device, dtype=torch.float32)
                 # the h^T dU partials go along where this backward's finish is queued until the whole backward
                 # pass is over (defer_grad_finish); a finish that runs at once -- its sums may be read by the
-                # next AccumulateGrad -- needs them now: their own launch, below
-                ride = wgrad and _DEFER[0] > 0
-                ws, splits = None, 0
-                if ride:
+                # next AccumulateGrad -- needs them now: their own launch (_pool_param_grads)
+                if wgrad and _DEFER[0] > 0:
                     splits = lib.sgg_xtw_splits(B, H, 512)
                     ws = torch.empty(splits * (H * 512 + 512), device=h.device, dtype=torch.float32)
-                ctx.pdh.put(dU, W1[:, E:], base, h, ws, splits, dh)
+                ctx.pdh.put(dU, W1h, base, h, ws, splits, dh)
             elif dual:
                 # dh = dU W1h (+ the other consumer's gradient of h) and the
                 # h^T dU partials (+ column sums) in ONE launch
                 dh = base if base is not None else torch.empty(B, H, device=h.device, dtype=torch.float32)
                 splits = lib.sgg_xtw_splits(B, H, 512)
                 ws = torch.empty(splits * (H * 512 + 512), device=h.device, dtype=torch.float32)
-                W1h = W1[:, E:]
-                acc = int(base is not None)
-
-                def launch2():
-                    N.check(lib.sgg_pool_dh_dw(N.ptr(dU), 512, N.ptr(W1h), W1h.stride(0), N.ptr(dh), dh.stride(0),
-                                               acc, N.ptr(h), h.stride(0), B, H, N.ptr(ws), ws.numel() * 4,
-                                               N.stream_ptr()), "sgg_pool_dh_dw")
-                launch2()
+                launch2 = _pool_dh_dw(dU, W1h, dh, base is not None, h, ws)
                 if timer.active:   # (re-issued like sgg_xw's accumulating launches: timing, not values)
                     mt = 4 if H >= 64 else (H + 15) // 16
                     timer.add("sgg::xw_xtw_kernel<%d>" % mt, (B, H), 4.0 * B * 512 * H,
                               4.0 * (2 * B * 512 + 512 * H + 2 * B * H) + 4.0 * ws.numel(), launch2)
             else:
                 # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
-                dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
+                dh = _pool_dh(dU, W1h, base, base is not None)
         if not wgrad:
-            return dh, None, None, None, None, None, None, None, None, None, None, None
-        # one launch after the dW1h partials: dW2, db2 (slab [dW2 | dA | db2]
-        # row sums), dW1h = dU^T h, dc = sum_j dU_j, and the fold backward
-        # of (dA, dc) -> dW1e, dWe, dbe
-        if (not dual and not hand) or (hand and ws is None):
-            ws, splits = xtw_partial(h, dU, colsum=True)
-        dW1 = torch.empty_like(W1)
-        dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
-        db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
-        dc = torch.empty(512, device=h.device, dtype=torch.float32)
-        gf = GradFinish()
-        gf.rowsum(part, rows, P, 0, bn * 512, dW2)
-        gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
-        gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
-        _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
-                              dW=dW1[:, :E])
-        gf.run()   # (with riding partials: queued, issued after the encoder's backward has written them)
-        return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None, None
+            return (dh,) + (None,) * 13
+        return (dh, None) + _pool_param_grads(h, W1, We, be, E, bn, dU, part, rows, ws, splits) + (None,) * 6
 
 
 class Handoff:
@@ -1540,13 +1654,10 @@ _PDH_OPEN = []
 def _pooldh_standalone(src):
     """The stand-alone launches of a taken slot: dh into buf, the partials into ws."""
     dU, W1h, base, h, ws, splits, buf = src
-    B, H = buf.shape
     if ws is not None:
-        N.check(_lib().sgg_pool_dh_dw(N.ptr(dU), 512, N.ptr(W1h), W1h.stride(0), N.ptr(buf), buf.stride(0),
-                                      int(base is not None), N.ptr(h), h.stride(0), B, H, N.ptr(ws), ws.numel() * 4,
-                                      N.stream_ptr()), "sgg_pool_dh_dw")
+        _pool_dh_dw(dU, W1h, buf, base is not None, h, ws)
     else:
-        xw_raw(dU, W1h, None, trans_w=False, prec="fp32", out=buf, act=0 if base is None else 2)
+        _pool_dh(dU, W1h, buf, base is not None)
 
 
 def pooldh_check():
@@ -1583,147 +1694,16 @@ def social_pool(h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, dh_in
     return out
 
 
-class _PoolDrop(torch.autograd.Function):
-    """_Pool for a pooling net built with dropout > 0, in training: the two
-    nn.Dropout of mlp_pre_pool as the stateless masks of include/sgg.h
-    "Pooling dropout masks" (drop = (p, seed, offset)), on the column-tiled
-    family's dropout form at EVERY width (sgg_pool_fwd_bn_drop /
-    sgg_pool_bwd_bn_drop) -- like every launch of that family fp32 in either
-    precision, never paired, no dh handoff.  Same arguments, outputs and
-    parameter gradients as _Pool."""
-
-    @staticmethod
-    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop):
-        lib = _lib()
-        p, seed, offset = float(drop[0]), int(drop[1]) & 0xFFFFFFFFFFFFFFFF, int(drop[2]) & 0xFFFFFFFF
-        if not 0.0 <= p < 1.0:
-            raise ValueError("pooling dropout p=%r outside [0, 1)" % p)
-        pool_is_wide(scenes)    # a scene above the tiled kernels' bound: ValueError before any launch
-        h = _rows(h, "h")
-        pos = _req(pos, "pos").contiguous()
-        B, Hd = h.shape
-        E = We.shape[0]
-        bn = W2.shape[0]
-        assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
-        assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
-        if bn > POOL_BN_MAX:
-            raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
-                                "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
-        # (a fixed-capacity batch refuses here, naming dropout, before the fold and the U product)
-        chunks, nchunks, max_rows, gpw = scenes.pool_plan(bn, family_bn=True, dropout=True)[:4]
-        W1, W2, b2 = W1.contiguous(), W2.contiguous(), b2.contiguous()
-        A, c = fold_fwd(W1[:, :E], We, be, b1)
-        U = xw_raw(h, W1[:, E:], c, trans_w=True)             # B x 512
-        out = torch.empty(B, bn, device=h.device, dtype=torch.float32)
-        am = torch.empty(B, bn, device=h.device, dtype=torch.int32)
-
-        def launch():
-            N.check(lib.sgg_pool_fwd_bn_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(b2),
-                                             N.ptr(scenes.scene_off), N.ptr(chunks), nchunks, max_rows, gpw, B, bn,
-                                             scenes.max_n, N.ptr(out), N.ptr(am), p, seed, offset, None,
-                                             N.stream_ptr()), "sgg_pool_fwd_bn_drop")
-        rider = _PRIDER[0]
-        if rider is not None:
-            rider.flush()    # a held forward goes out first, on its own
-        launch()
-        if timer.active:
-            nb = 4.0 * (B * 512 + 2 * B) + 8.0 * B * bn
-            timer.add("sgg::pool_fwd_bn_drop_kernel", (scenes.S, B), _pool_flops_bn(scenes, bn), nb + _pool_wbytes(bn),
-                      launch)
-        ctx.scenes, ctx.E, ctx.link, ctx.drop = scenes, E, link, (p, seed, offset)
-        ctx.save_for_backward(h, pos, W1, We, be, A, W2, U, out, am)
-        ctx.mark_non_differentiable(am)
-        ctx.set_materialize_grads(False)
-        return out, am
-
-    @staticmethod
-    def backward(ctx, dout, _dam):
-        lib = _lib()
-        h, pos, W1, We, be, A, W2, U, out, am = ctx.saved_tensors
-        sc, E = ctx.scenes, ctx.E
-        p, seed, offset = ctx.drop
-        B, bn = out.shape
-        H = h.shape[1]
-        dout = dout.contiguous()
-        need = ctx.needs_input_grad
-        wgrad = any(need[2:8])       # False: weights frozen, input gradient only
-        P = bn * 512 + 1024 + bn
-        dU = torch.empty(B, 512, device=h.device, dtype=torch.float32)
-        rows = lib.sgg_pool_bwd_bn_grid(sc.S, bn, sc.max_n)
-        nws = lib.sgg_pool_bwd_bn_ws_floats(sc.S, B, bn, sc.max_n)
-        if rows < 0 or nws < 0:
-            N.check(-1, "sgg_pool_bwd_bn_ws_floats")
-        part = torch.empty(nws, device=h.device, dtype=torch.float32) if wgrad else None
-
-        def launch():
-            N.check(lib.sgg_pool_bwd_bn_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
-                                             N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, sc.max_n, N.ptr(dU),
-                                             N.ptr(part), nws if wgrad else 0, p, seed, offset, None,
-                                             N.stream_ptr()), "sgg_pool_bwd_bn_drop")
-        launch()
-        if timer.active:
-            nb = 8.0 * B * 512 + 12.0 * B * bn + 4.0 * 512 * (2 + bn) + (4.0 * nws if wgrad else 0.0)
-            name = "sgg::pool_bwd_bn_du_drop_kernel<%s>%s" % (("true", " + sgg::pool_bwd_bn_dw_drop_kernel") if wgrad
-                                                             else ("false", ""))
-            timer.add(name, (sc.S, B), 8.0 * B * bn * 512, nb, launch)
-        dh = None
-        if need[0]:
-            # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
-            base = ctx.link.take() if ctx.link is not None else None
-            dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
-        if not wgrad:
-            return dh, None, None, None, None, None, None, None, None, None, None
-        # as _Pool.backward: the slab's row sums, dW1h = dU^T h, dc, the fold backward of (dA, dc)
-        ws, splits = xtw_partial(h, dU, colsum=True)
-        dW1 = torch.empty_like(W1)
-        dW2 = torch.empty(bn, 512, device=h.device, dtype=torch.float32)
-        db2 = torch.empty(bn, device=h.device, dtype=torch.float32)
-        dc = torch.empty(512, device=h.device, dtype=torch.float32)
-        gf = GradFinish()
-        gf.rowsum(part, rows, P, 0, bn * 512, dW2)
-        gf.rowsum(part, rows, P, bn * 512 + 1024, bn, db2)
-        gf.xtw_sums(ws, splits, H, 512, dW1[:, E:], trans_c=True, colsum=dc)
-        _, dWe, dbe = gf.fold(W1[:, :E], We, be, part, rows, P, bn * 512, ws[splits * H * 512:], splits, 512, 0,
-                              dW=dW1[:, :E])
-        gf.run()
-        return dh, None, dW1, dWe, dbe, dc, dW2, db2, None, None, None
-
-
-class _PoolDropPos(torch.autograd.Function):
-    """_PoolDrop with the gradient of the positions (sgg_pool_dpos_drop), as
-    _PoolPos is to _Pool: the per-step rollout pools at predicted positions."""
-
-    @staticmethod
-    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop):
-        return _PoolDrop.forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, drop)
-
-    @staticmethod
-    def backward(ctx, dout, _dam):
-        # (one pooling net at every step: its parameter gradients are written now, see _PoolPos.backward)
-        prev, _DEFER[0] = _DEFER[0], 0
-        try:
-            grads = list(_PoolDrop.backward(ctx, dout, _dam))
-        finally:
-            _DEFER[0] = prev
-        if ctx.needs_input_grad[1]:
-            _h, pos, _W1, _We, _be, A, W2, U, out, am = ctx.saved_tensors
-            sc = ctx.scenes
-            p, seed, offset = ctx.drop
-            B, bn = out.shape
-            dout = dout.contiguous()
-            dpos = torch.empty(B, 2, device=pos.device, dtype=torch.float32)
-            N.check(_lib().sgg_pool_dpos_drop(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am),
-                                              N.ptr(dout), N.ptr(sc.scene_off), sc.S, B, bn, N.ptr(dpos), p, seed,
-                                              offset, None, N.stream_ptr()), "sgg_pool_dpos_drop")
-            grads[1] = dpos
-        return tuple(grads)
+def social_pool_pos(h, pos, W1, We, be, b1, W2, b2, scenes, U=None):
+    """social_pool whose backward also returns the gradient of pos."""
+    out, _ = _Pool.apply(h, pos, W1, We, be, b1, W2, b2, scenes, None, U, None, None, True)
+    return out
 
 
 def social_pool_drop(h, pos, W1, We, be, b1, W2, b2, scenes, drop, link=None, pos_grad=False):
     """social_pool / social_pool_pos of a pooling net with dropout > 0 in
     training; drop = (p, seed, offset), one (seed, offset) per forward."""
-    op = _PoolDropPos if pos_grad else _PoolDrop
-    out, _ = op.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, drop)
+    out, _ = _Pool.apply(h, pos, W1, We, be, b1, W2, b2, scenes, link, None, None, drop, pos_grad)
     return out
 
 
@@ -1764,9 +1744,7 @@ def pool_norm_check(scenes, bn, norms, dropout=0.0):
     if dropout > 0:
         raise NotImplementedError("social pooling: batch_norm together with dropout > 0 in train() is not supported "
                                   "(the batch_norm kernels have no dropout form)")
-    if bn > POOL_BN_MAX:
-        raise N.NativeError("social pooling: bottleneck_dim=%d exceeds the pooling kernels' bound of %d "
-                            "(SGG_POOL_BN_MAX)" % (bn, POOL_BN_MAX))
+    _pool_bn_bound(bn)
     scenes.pool_plan(bn, batch_norm=True)     # a fixed-capacity batch refuses here, naming batch_norm
     import numpy as np
     sizes = np.diff(np.asarray(scenes.host_off))
@@ -1791,24 +1769,18 @@ class _PoolNorm(torch.autograd.Function):
     (sgg_pool_norm_running).  g1 / t1, g2 / t2: the BatchNorm weights and
     biases; stats = per layer (eps, momentum, running_mean, running_var,
     num_batches_tracked).  The three biases in front of a BatchNorm (be, b1,
-    b2) get exact zeros as gradients."""
+    b2) get exact zeros as gradients.  want_dpos: as _Pool's pos_grad (the
+    kernel writes the gradient of pos itself)."""
 
     @staticmethod
     def forward(ctx, h, pos, W1, We, be, b1, g1, t1, W2, b2, g2, t2, scenes, link, stats, min_n, want_dpos):
         lib = _lib()
         (eps1, mom1, rm1, rv1, nbt1), (eps2, mom2, rm2, rv2, nbt2) = stats
-        h = _rows(h, "h")
-        pos = _req(pos, "pos").contiguous()
-        B, Hd = h.shape
-        E = We.shape[0]
-        bn = W2.shape[0]
-        S = scenes.S
-        assert pos.shape == (B, 2) and scenes.B == B, (pos.shape, B, scenes.B)
-        assert W1.shape == (512, E + Hd), (W1.shape, E, Hd)
-        W1, W2, b2 = W1.contiguous(), W2.contiguous(), b2.contiguous()
         g1, t1, g2, t2 = g1.contiguous(), t1.contiguous(), g2.contiguous(), t2.contiguous()
-        A, c = fold_fwd(W1[:, :E], We, be, b1)
-        U = xw_raw(h, W1[:, E:], c, trans_w=True, prec="fp32")             # B x 512, fp32 in either precision
+        # (U fp32 in either precision)
+        h, pos, W1, W2, b2, A, U, out, am, _ = _pool_operands(h, pos, W1, We, be, b1, W2, b2, scenes, prec="fp32")
+        B, bn = out.shape
+        S = scenes.S
         dev, f32 = h.device, torch.float32
         Un = torch.empty(B, 512, device=dev, dtype=f32)
         An = torch.empty(S, 1024, device=dev, dtype=f32)
@@ -1816,8 +1788,6 @@ class _PoolNorm(torch.autograd.Function):
         var1 = torch.empty(S, 512, device=dev, dtype=f32)
         mu2 = torch.empty(S, bn, device=dev, dtype=f32)
         var2 = torch.empty(S, bn, device=dev, dtype=f32)
-        out = torch.empty(B, bn, device=dev, dtype=f32)
-        am = torch.empty(B, bn, device=dev, dtype=torch.int32)
 
         def launch():
             N.check(lib.sgg_pool_norm_fwd(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(g1), N.ptr(t1), N.ptr(W2), N.ptr(b2),
@@ -1825,28 +1795,28 @@ class _PoolNorm(torch.autograd.Function):
                                           scenes.max_n, eps1, eps2, N.ptr(Un), N.ptr(An), N.ptr(mu1), N.ptr(var1),
                                           N.ptr(mu2), N.ptr(var2), N.ptr(out), N.ptr(am), N.stream_ptr()),
                     "sgg_pool_norm_fwd")
-        rider = _PRIDER[0]
-        if rider is not None:
-            rider.flush()    # a held forward goes out first, on its own
-        launch()
-        if timer.active:
-            nb = 4.0 * (2 * B * 512 + 2 * B) + 8.0 * B * bn
-            timer.add("sgg::pool_norm_fwd_kernel", (S, B), 2.0 * _pool_flops_bn(scenes, bn), nb + _pool_wbytes(bn),
-                      launch)
+        _pool_alone(launch, scenes, bn, 2.0, _pool_flops_bn, 4.0 * (2 * B * 512 + 2 * B) + 8.0 * B * bn,
+                    "sgg::pool_norm_fwd_kernel")
         for mean, var, C, mom, rm, rv, nbt in ((mu1, var1, 512, mom1, rm1, rv1, nbt1),
                                                (mu2, var2, bn, mom2, rm2, rv2, nbt2)):
             N.check(lib.sgg_pool_norm_running(N.ptr(mean), N.ptr(var), N.ptr(scenes.scene_off), S, C, mom,
                                               N.ptr(rm), N.ptr(rv), N.stream_ptr()), "sgg_pool_norm_running")
             if nbt is not None:
                 nbt.add_(S)
-        ctx.scenes, ctx.E, ctx.link, ctx.eps, ctx.min_n, ctx.want_dpos = scenes, E, link, (eps1, eps2), min_n, want_dpos
-        ctx.save_for_backward(h, pos, W1, We, be, A, g1, W2, b2, g2, t2, U, Un, An, mu1, var1, mu2, var2, out, am)
-        ctx.mark_non_differentiable(am)
-        ctx.set_materialize_grads(False)
+        ctx.eps, ctx.min_n, ctx.want_dpos = (eps1, eps2), min_n, want_dpos
+        _pool_save(ctx, scenes, We.shape[0], link, am, h, pos, W1, We, be, A, g1, W2, b2, g2, t2, U, Un, An, mu1, var1,
+                   mu2, var2, out, am)
         return out, am
 
     @staticmethod
     def backward(ctx, dout, _dam):
+        if not ctx.want_dpos:
+            return _PoolNorm._grads(ctx, dout)
+        with _grads_written_now():
+            return _PoolNorm._grads(ctx, dout)
+
+    @staticmethod
+    def _grads(ctx, dout):
         lib = _lib()
         h, pos, W1, We, be, A, g1, W2, b2, g2, t2, U, Un, An, mu1, var1, mu2, var2, out, am = ctx.saved_tensors
         sc, E = ctx.scenes, ctx.E
@@ -1881,7 +1851,7 @@ class _PoolNorm(torch.autograd.Function):
         if need[0]:
             # dh = dU W1h (+ the other consumer's gradient of h, accumulated in the same launch)
             base = ctx.link.take() if ctx.link is not None else None
-            dh = xw_raw(dU, W1[:, E:], None, trans_w=False, prec="fp32", out=base, act=0 if base is None else 2)
+            dh = _pool_dh(dU, W1[:, E:], base, base is not None)
         if not wgrad:
             return (dh, dpos) + (None,) * 15
         # the two slabs' row sums, dW1h = dU^T h, the fold backward of dA; the biases in front of a BatchNorm
@@ -1911,24 +1881,6 @@ class _PoolNorm(torch.autograd.Function):
                 dW2, torch.zeros(bn, device=dev, dtype=torch.float32), dg2, dt2, None, None, None, None, None)
 
 
-class _PoolNormPos(torch.autograd.Function):
-    """_PoolNorm called once per step of the per-step rollout: one pooling net
-    at every step, so its parameter gradients are written now, not queued (see
-    _PoolPos.backward)."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        return _PoolNorm.forward(ctx, *args)
-
-    @staticmethod
-    def backward(ctx, dout, _dam):
-        prev, _DEFER[0] = _DEFER[0], 0
-        try:
-            return _PoolNorm.backward(ctx, dout, _dam)
-        finally:
-            _DEFER[0] = prev
-
-
 def social_pool_norm(h, pos, pool, scenes, link=None, pos_grad=False):
     """PoolHiddenNet core for a net built with batch_norm=1 in train()
     (batch statistics per scene, running statistics updated): pool is the
@@ -1941,9 +1893,8 @@ def social_pool_norm(h, pos, pool, scenes, link=None, pos_grad=False):
     min_n = pool_norm_check(scenes, l2.weight.shape[0], (n1, n2), dropout=pool.dropout)
     stats = tuple((float(m.eps), float(m.momentum), m.running_mean, m.running_var, m.num_batches_tracked)
                   for m in (n1, n2))
-    op = _PoolNormPos if pos_grad else _PoolNorm
-    out, _ = op.apply(h, pos, l1.weight, emb.weight, emb.bias, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias,
-                      n2.weight, n2.bias, scenes, link, stats, min_n, bool(pos_grad))
+    out, _ = _PoolNorm.apply(h, pos, l1.weight, emb.weight, emb.bias, l1.bias, n1.weight, n1.bias, l2.weight,
+                             l2.bias, n2.weight, n2.bias, scenes, link, stats, min_n, bool(pos_grad))
     return out
 
 
@@ -4259,44 +4210,6 @@ def dec_step_enabled():
     """SGG_DEC_STEP=0 keeps the per-op decoder loop (stock nn.LSTM + one
     launch per layer); read at every call, so one process can alternate."""
     return os.environ.get("SGG_DEC_STEP", "1") != "0"
-
-
-class _PoolPos(torch.autograd.Function):
-    """_Pool with the gradient of the positions (sgg_pool_dpos): the per-step
-    rollout pools at predicted positions (models.py:160, :164).  Same
-    arguments, pooling launches and parameter gradients as _Pool."""
-
-    @staticmethod
-    def forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link=None, U=None, pdh=None):
-        return _Pool.forward(ctx, h, pos, W1, We, be, b1, W2, b2, scenes, link, U, pdh)
-
-    @staticmethod
-    def backward(ctx, dout, _dam):
-        # the loop calls one pooling net at every step, so autograd SUMS this op's parameter gradients with
-        # the other steps': they must be written now, not at the trainer's grad_flush (defer_grad_finish's
-        # invariant -- no parameter feeds two ops -- does not hold here)
-        prev, _DEFER[0] = _DEFER[0], 0
-        try:
-            grads = list(_Pool.backward(ctx, dout, _dam))
-        finally:
-            _DEFER[0] = prev
-        if ctx.needs_input_grad[1]:
-            _h, pos, _W1, _We, _be, A, W2, U, out, am = ctx.saved_tensors
-            sc = ctx.scenes
-            B, bn = out.shape
-            dout = dout.contiguous()
-            dpos = torch.empty(B, 2, device=pos.device, dtype=torch.float32)
-            N.check(_lib().sgg_pool_dpos(N.ptr(U), N.ptr(pos), N.ptr(A), N.ptr(W2), N.ptr(out), N.ptr(am), N.ptr(dout),
-                                         N.ptr(sc.scene_off), sc.S, B, bn, N.ptr(dpos), N.stream_ptr()),
-                    "sgg_pool_dpos")
-            grads[1] = dpos
-        return tuple(grads)
-
-
-def social_pool_pos(h, pos, W1, We, be, b1, W2, b2, scenes, U=None):
-    """social_pool whose backward also returns the gradient of pos."""
-    out, _ = _PoolPos.apply(h, pos, W1, We, be, b1, W2, b2, scenes, None, U, None)
-    return out
 
 
 def dec_step_ok(H, bn, mlp_dim, NU=512):

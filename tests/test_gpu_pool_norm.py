@@ -31,7 +31,7 @@ def _apply(net, h, pos, sc, pos_grad=True):
     min_n = K.pool_norm_check(sc, l2.weight.shape[0], (n1, n2), dropout=net.dropout)
     stats = tuple((float(m.eps), float(m.momentum), m.running_mean, m.running_var, m.num_batches_tracked)
                   for m in (n1, n2))
-    op = K._PoolNormPos if pos_grad else K._PoolNorm
+    op = K._PoolNorm
     return op.apply(h, pos, l1.weight, emb.weight, emb.bias, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias,
                     n2.weight, n2.bias, sc, None, stats, min_n, pos_grad)
 
